@@ -8,11 +8,18 @@ HBM.  Multi-GPU: one process per GPU, each rank encodes its own stripe (stripes
 are independent, encode.rs:30-80 -> no data-path collective; weak scaling).  The
 barrier / max-time reduction are timing plumbing only and run over gloo (no RCCL).
 
-    python bench.py                      # N = 1
+    python bench.py                      # N = 1: the headline figure only
+    python bench.py --full               # + oracle check, host path, small stripes, config legs, CPU baselines
+    python bench.py --dump-outputs DIR   # + the last timed step's parity as DIR/parity.npy
     python bench.py --gpus 8             # spawns 8 ranks itself (no torchrun needed)
     torchrun --nproc-per-node 8 bench.py --gpus 8   # same, launched externally
 
+A plain run sets up, warms up, times --steps encodes and prints one JSON line; everything
+that takes runs of its own (below: cpu_baseline*, and the verification against the oracle,
+host_inclusive*, gpu_small_stripes, config_legs) is measured with --full only and null or absent without.
+
 value       = ranks * padded stripe bytes * steps / max-over-ranks wall time, GiB/s
+ms_per_step = max-over-ranks wall time / steps, in milliseconds
 roofline    = algorithmic bytes per launch (read 10 + write 4 chunks =
               1,503,244,288 B) / mean kernel time (HIP events on the launch
               stream) vs 8 TB/s HBM peak
@@ -45,6 +52,8 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
 # streams at 5,090 GB/s with plain loads/stores in the same sweep)
 COPY_CEILING_GBS = 5546.0
 VERIFY_W = 4096         # positions per verified column slice (every rank, both ends)
+DUMP_BUDGET_BYTES = 32 << 20  # --dump-outputs: float32 bytes written, all ranks together
+DUMP_SEED = 20240607          # --dump-outputs: sampled byte positions of a large parity
 
 
 def parse(argv=None):
@@ -57,13 +66,22 @@ def parse(argv=None):
                          "steps see the GPU at its sustained clock (an idle MI355X needs ~0.1 s of "
                          "load to ramp: 5 warmups gave 0.44 ms/launch, 200 gave 0.385)")
     ap.add_argument("--stripe-bytes", type=int, default=STRIPE_BYTES)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: the "
+                         "oracle check of the parity, the host-inclusive encodes, the small-stripe "
+                         "rates, the legs of BASELINE configs 2, 3 and 5 and the CPU baselines (each "
+                         "can be switched off below); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the parity of the last step to DIR/parity.npy "
+                         "(float32; a fixed seeded sample of byte positions when the parity is large)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="bound on the headline CPU-baseline sample (0 disables all CPU legs)")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true")
-    ap.add_argument("--no-small", action="store_true", help="skip the clay_bench-size GPU batch rates")
+                    help="--full: bound on the headline CPU-baseline sample (0 disables all CPU legs)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the oracle check of the parity")
+    ap.add_argument("--no-host-path", action="store_true", help="--full: skip the host-inclusive encodes")
+    ap.add_argument("--no-small", action="store_true",
+                    help="--full: skip the clay_bench-size GPU batch rates")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the driver-timed legs of BASELINE configs 2, 3 and 5 (after the timed region)")
+                    help="--full: skip the driver-timed legs of BASELINE configs 2, 3 and 5 (after the timed region)")
     ap.add_argument("--leg-calls", type=int, default=30, help="timed calls per config leg")
     ap.add_argument("--path", default="auto",
                     choices=["auto", "fused", "staged", "bitsliced", "stream"])
@@ -96,8 +114,9 @@ def launch(args, argv) -> int:
     rank's code.  The parent never touches HIP."""
     port = _free_port()
     # build the CPU checker once here (CPU only, no HIP) so the ranks never race on make
-    from oracle import oracle
-    oracle.build()
+    if args.cpu_dry or args.full:
+        from oracle import oracle
+        oracle.build()
     procs = []
     for r in range(args.gpus):
         env = dict(os.environ)
@@ -453,6 +472,24 @@ def config_legs(torch, dev, local, stream, oracle_cls, calls: int):
     return out
 
 
+def dump_outputs(torch, dirpath, parity, world: int, rank: int):
+    """--dump-outputs: what the timed path's caller holds after the last timed step, the parity
+    of this rank's stripe ((M, chunk) bytes), as float32 in DIR/parity.npy (parity_rank<r>.npy
+    at N > 1).  A parity larger than the budget is sampled at the same byte positions of every
+    parity chunk: both ends plus positions drawn from a fixed seed, so two builds run with the
+    same arguments write arrays that compare element for element (the inputs are seeded too)."""
+    os.makedirs(dirpath, exist_ok=True)
+    chunk = parity.shape[1]
+    cols = DUMP_BUDGET_BYTES // 4 // max(1, world) // M
+    if chunk > cols:
+        w = min(VERIFY_W, cols // 4)
+        pos = np.random.default_rng(DUMP_SEED).integers(0, chunk, cols - 2 * w, dtype=np.int64)
+        pos = np.unique(np.concatenate([np.arange(w), pos, np.arange(chunk - w, chunk)]))
+        parity = parity[:, torch.from_numpy(pos).to(parity.device)]
+    name = "parity.npy" if world == 1 else f"parity_rank{rank}.npy"
+    np.save(os.path.join(dirpath, name), parity.cpu().numpy().astype(np.float32))
+
+
 def latest_traffic():
     """Per-launch HBM bytes from the newest committed PMC summary (profiles/*encode*_pmc.json)."""
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*encode*_pmc.json")))
@@ -487,30 +524,38 @@ def run_rank(args) -> int:
         # control plane -- the start / stop barrier and the all_gather of three doubles per rank
         # -- needs no RCCL bring-up across the node (north_star: "RCCL unused")
         dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=args.dist_timeout))
-    from oracle import oracle  # checker / CPU legs only (and the dry run's stand-in encode)
-    oracle.build()
-
-    ocode = oracle.OracleClay(K, M, D)
-    chunk = ocode.encoded_chunk_size(args.stripe_bytes)
+    oracle = None
+    if args.cpu_dry or args.full:
+        from oracle import oracle  # checker / CPU legs only (and the dry run's stand-in encode)
+        oracle.build()
+    if args.cpu_dry:
+        sizer = ocode = oracle.OracleClay(K, M, D)
+    else:
+        import clay_amd
+        from clay_amd import ClayCode
+        sizer = code = ClayCode(K, M, D)
+    chunk = sizer.encoded_chunk_size(args.stripe_bytes)
     padded = chunk * K
-    alpha = ocode.sub_chunk_no
+    alpha = sizer.sub_chunk_no
     sc = chunk // alpha
     path, launches = "oracle-cpu-dry", 0
     verified = None
 
     if args.cpu_dry:
         host = np.random.default_rng(1234 + rank).integers(0, 256, padded, dtype=np.uint8)
-        step = lambda: ocode.encode_array(host)  # noqa: E731
+        last = {}
+
+        def step():
+            last["enc"] = ocode.encode_array(host)
+
         sync = lambda: None  # noqa: E731
         dev_t = torch.device("cpu")
     else:
         torch.cuda.set_device(local)
         dev_t = torch.device("cuda", local)
-        import clay_amd
-        from clay_amd import ClayCode
         clay_amd.set_encode_path(args.path, args.tile)
-        code = ClayCode(K, M, D)
-        assert code.encoded_chunk_size(args.stripe_bytes) == chunk
+        if oracle is not None:
+            assert oracle.OracleClay(K, M, D).encoded_chunk_size(args.stripe_bytes) == chunk
         g = torch.Generator(device=dev_t)
         g.manual_seed(1234 + rank)
         data = torch.randint(0, 256, (K, chunk), dtype=torch.uint8, device=dev_t, generator=g)
@@ -556,11 +601,16 @@ def run_rank(args) -> int:
         verified = True
     else:
         kern_ms = [a.elapsed_time(b) for a, b in evs]
-        if not args.no_verify:
-            verified = verify_slices(code, data, par, chunk, oracle.OracleClay)
+    if args.dump_outputs:
+        # the last timed step's parity, before any later leg touches the buffers
+        dump_outputs(torch, args.dump_outputs, torch.from_numpy(last["enc"][K:]) if args.cpu_dry else par,
+                     world, rank)
+    if args.full and not args.cpu_dry and not args.no_verify:
+        verified = verify_slices(code, data, par, chunk, oracle.OracleClay)
 
     # per-rank wall / kernel mean / verified -> every rank (max over ranks is the job time)
-    mine = torch.tensor([el, float(np.mean(kern_ms)), 0.0 if verified is False else 1.0],
+    # verified: 1 / 0, or -1 when this run made no check (no --full, or --no-verify)
+    mine = torch.tensor([el, float(np.mean(kern_ms)), -1.0 if verified is None else float(verified)],
                         dtype=torch.float64)  # CPU tensor: the gloo group carries it
     if world > 1:
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -571,7 +621,7 @@ def run_rank(args) -> int:
     tmax = max(p[0] for p in per)
 
     host_incl = host_sync = small = legs = None
-    if rank == 0 and world == 1 and not args.cpu_dry:
+    if args.full and rank == 0 and world == 1 and not args.cpu_dry:
         if not args.no_host_path:
             # PCIe-inclusive: pinned host data chunks -> device -> parity back to
             # pinned host memory.  host_sync: one stream, whole-stripe copies; host_incl: the
@@ -632,7 +682,7 @@ def run_rank(args) -> int:
                    "launches_per_step": launches, "prewarm_ms": args.prewarm_ms},
         "per_rank": {"wall_ms_per_step": [round(p[0] / args.steps * 1e3, 4) for p in per],
                      "kernel_ms_mean": [round(p[1], 4) for p in per],
-                     "verified": [bool(p[2]) for p in per]},
+                     "verified": [None if p[2] < 0 else bool(p[2]) for p in per]},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": traffic, "traffic_source": traffic_src,
@@ -640,7 +690,8 @@ def run_rank(args) -> int:
                      "frac_of_measured_copy": round(achieved / COPY_CEILING_GBS, 4),
                      "algorithmic_bytes_per_launch": algo_bytes,
                      "kernel_ms_mean": round(mean_ms, 4), "kernel_ms_min": round(min(kern_ms), 4)},
-        "verified_vs_oracle": verified if world == 1 else all(bool(p[2]) for p in per),
+        "verified_vs_oracle": (verified if world == 1 or any(p[2] < 0 for p in per)
+                               else all(bool(p[2]) for p in per)),
         "host_inclusive_GiBps": host_incl,
         "host_inclusive_sync_GiBps": host_sync,
         "gpu_small_stripes": small,
@@ -648,7 +699,7 @@ def run_rank(args) -> int:
     }
     if args.cpu_dry:
         out["cpu_dry"] = True
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
         info = host_info()
         threads = all_cores_threads(info)
         one, allc = cpu_baseline_headline(args.cpu_seconds, threads)

@@ -47,6 +47,87 @@ def test_bench_launcher_cpu_dry(oracle_mod, world):
         assert key in d
 
 
+EXTRA_KEYS = ("cpu_baseline", "cpu_baseline_all_cores", "cpu_baseline_cfg1", "host")
+
+
+def test_bench_plain_run_dumps_parity_and_skips_extras(oracle_mod, tmp_path):
+    """A plain run measures the headline only (no CPU baselines even when --cpu-seconds asks
+    for them) and --dump-outputs writes the last step's parity: float32, the whole (M, chunk)
+    array at this size, equal to the oracle's parity of the seeded input."""
+    import numpy as np
+    stripe = 10 * 256 * 2 * 64
+    d = _run(["--cpu-dry", "--stripe-bytes", str(stripe), "--steps", "2", "--warmup", "1",
+              "--cpu-seconds", "0.3", "--dump-outputs", str(tmp_path / "dump")])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    for key in EXTRA_KEYS:
+        assert key not in d
+    for key in ("host_inclusive_GiBps", "gpu_small_stripes", "config_legs"):
+        assert d[key] is None
+    assert [p.name for p in (tmp_path / "dump").iterdir()] == ["parity.npy"]
+    got = np.load(tmp_path / "dump" / "parity.npy")
+    padded = d["config"]["padded_stripe_bytes"]
+    host = np.random.default_rng(1234).integers(0, 256, padded, dtype=np.uint8)
+    ref = oracle_mod.OracleClay(10, 4, 13).encode_array(host)[10:]
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert np.array_equal(got, ref.astype(np.float32))
+
+
+def test_bench_full_adds_cpu_baselines(oracle_mod):
+    stripe = 10 * 256 * 2 * 64
+    d = _run(["--cpu-dry", "--full", "--stripe-bytes", str(stripe), "--steps", "2", "--warmup", "1",
+              "--cpu-seconds", "0.3"])
+    for key in EXTRA_KEYS:
+        assert key in d
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["cores"] == 1
+    assert d["cpu_baseline_cfg1"]["encode"]["single_thread"] > 0
+
+
+def test_bench_dump_samples_a_large_parity_reproducibly(tmp_path):
+    """A parity above the dump budget is sampled at fixed positions (both ends and seeded draws,
+    the same for every parity chunk): two dumps of the same parity are identical, stay inside
+    the budget and hold the parity's own bytes at those positions."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.M == 4
+    chunk = bench.DUMP_BUDGET_BYTES // 4 // bench.M + 100_003
+    # byte p of parity chunk i is byte i of p, so a dumped column names the position it came from
+    par = torch.from_numpy(np.arange(chunk, dtype="<u4").view(np.uint8).reshape(chunk, 4).T.copy())
+    for sub in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / sub), par, 1, 0)
+    a, b = np.load(tmp_path / "a" / "parity.npy"), np.load(tmp_path / "b" / "parity.npy")
+    assert a.dtype == np.float32 and a.shape[0] == bench.M and a.nbytes <= bench.DUMP_BUDGET_BYTES
+    assert np.array_equal(a, b)
+    pos = (a.astype(np.int64) * (256 ** np.arange(4))[:, None]).sum(axis=0)
+    assert (np.diff(pos) > 0).all() and pos[-1] == chunk - 1 and pos.size > chunk // 2
+    w = bench.VERIFY_W
+    assert np.array_equal(pos[:w], np.arange(w)) and np.array_equal(pos[-w:], np.arange(chunk - w, chunk))
+
+
+@pytest.mark.gpu
+def test_bench_gpu_dump_matches_oracle(oracle_mod, torch_cuda, tmp_path):
+    """The real device path at a small ragged stripe (sc = 8 mod 16): the dumped parity of a
+    plain run is the oracle's parity of the same seeded device input."""
+    import numpy as np
+    torch = torch_cuda
+    sc = 16 * 300 + 8
+    stripe = 10 * 256 * sc
+    d = _run(["--stripe-bytes", str(stripe), "--steps", "2", "--warmup", "1", "--prewarm-ms", "0",
+              "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["config"]["sub_chunk_bytes"] == sc
+    assert d["verified_vs_oracle"] is None and d["per_rank"]["verified"] == [None]
+    assert d["config_legs"] is None and "cpu_baseline" not in d
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    data = torch.randint(0, 256, (10, 256 * sc), dtype=torch.uint8, device=dev, generator=g)
+    ref = oracle_mod.OracleClay(10, 4, 13).encode_array(data.cpu().numpy().reshape(-1))[10:]
+    got = np.load(tmp_path / "parity.npy")
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert np.array_equal(got, ref.astype(np.float32))
+
+
 def test_bench_launcher_rank_failure_stops_job(oracle_mod):
     """A rank that dies before the rendezvous (bad ordinal, OOM ...) must not leave the
     other rank blocked in init / barrier: the launcher sees the first non-zero exit,
