@@ -129,7 +129,8 @@ def set_exec_mode(mode: str) -> str:
 
 def last_exec_path() -> str:
     """Plan executor of this thread's last decode / repair / staged encode: 'tile' | 'grouped' |
-    'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-repair-stream' | 'bs-repair' | 'none'."""
+    'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
+    'bs-decode1-batch' | 'grouped-batch' (the batched decodes) | 'none'."""
     return _lib.lib().clay_last_exec_path().decode()
 
 
@@ -361,6 +362,42 @@ class ClayCode:
         fn = _lib.lib().clay_decode_device_codeword if codeword else _lib.lib().clay_decode_device
         rc = fn(C.byref(self._c), cp, _sizes(er), len(er), op, int(chunk_size), int(device),
                 C.c_void_p(int(stream)), C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def decode_device_strided(self, chunks, erasures: Sequence[int], out, n_stripes: int, chunk_size: int,
+                              node_stride: int = 0, stripe_stride: int = 0, out_node_stride: int = 0,
+                              out_stripe_stride: int = 0, device: int = 0, stream: int = 0):
+        """Batched decode of stripes with the same erasure set at fixed strides (clay.h
+        clay_decode_device_strided): every erased node e of stripe s is rebuilt at
+        out + s * out_stripe_stride + e * out_node_stride; out may be chunks (in place).
+        Strides default to a contiguous [n_stripes][n][chunk_size] layout."""
+        ns_ = node_stride or chunk_size
+        ss_ = stripe_stride or self.n * chunk_size
+        ons = out_node_stride or chunk_size
+        oss = out_stripe_stride or self.n * chunk_size
+        er = list(erasures)
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_decode_device_strided(C.byref(self._c), C.c_void_p(_ptr(chunks)), ns_, ss_,
+                                                   _sizes(er), len(er), C.c_void_p(_ptr(out)), ons, oss,
+                                                   int(n_stripes), int(chunk_size), int(device),
+                                                   C.c_void_p(int(stream)), C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def decode_device_batch(self, chunks, erasures: Sequence[int], out_chunks, n_stripes: int, chunk_size: int,
+                            device: int = 0, stream: int = 0):
+        """Batched decode, pointer-array form (clay.h clay_decode_device_batch): chunks /
+        out_chunks hold n_stripes * n entries, stripe s at [s * n, s * n + n), None where absent
+        as for decode_device; the None pattern must be the same in every stripe."""
+        cnt = max(1, self.n * int(n_stripes))
+        cp = (C.c_void_p * cnt)(*[(_ptr(x) if x is not None else None) for x in chunks])
+        op = (C.c_void_p * cnt)(*[(_ptr(x) if x is not None else None) for x in out_chunks])
+        er = list(erasures)
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_decode_device_batch(C.byref(self._c), cp, _sizes(er), len(er), op, int(n_stripes),
+                                                 int(chunk_size), int(device), C.c_void_p(int(stream)),
+                                                 C.byref(err))
         if rc:
             _raise(rc, err)
 

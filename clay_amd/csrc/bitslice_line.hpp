@@ -123,17 +123,31 @@ struct Dec1Kernel {
         }
     }
 
-    template <bool FULL, bool BT>
+    // BATCH: b0 = the tile's first column (32 positions of one stripe, Dec1Args); the lane's
+    // column gives its stripe, its position in the sub-chunk and the stripe's input / output offsets
+    template <bool FULL, bool BT, bool BATCH = false>
     __device__ static void tile(const Dec1Args &a, uint64_t b0) {
         for (int u = threadIdx.x; u < UNITS; u += BLOCK) {
             const int pg = u % PG, line = u / PG;
             const int hi = line / wt(YE), lo = line % wt(YE);
             const uint32_t z0 = uint32_t(hi * wt(YE) * Q + lo);  // the line's layer with digit ye = 0
-            const uint64_t pos = b0 + uint64_t(32 * pg);
+            uint64_t pos, ip, op;  // position in the sub-chunk; + the stripe's offset: reads, writes
+            if constexpr (BATCH) {
+                const uint64_t col = b0 + uint64_t(pg);
+                const uint32_t stripe = uint32_t(col) / a.cps;
+                // columns past the last stripe: pos = sc, no byte is touched (nv = 0)
+                pos = FULL || col < a.ncols ? uint64_t(32u * (uint32_t(col) - stripe * a.cps)) : a.sc;
+                ip = uint64_t(int64_t(stripe) * a.sin) + pos;
+                op = uint64_t(int64_t(stripe) * a.sout) + pos;
+            } else {
+                pos = b0 + uint64_t(32 * pg);
+                ip = pos;
+                op = pos;
+            }
             const int nv = FULL ? (BT ? 32 : 4)
                          : BT ? int(pos >= a.sc ? 0 : a.sc - pos > 32 ? 32 : a.sc - pos)                // bytes
                               : int(pos >= a.sc ? 0 : (a.sc - pos) / 8 > 4 ? 4 : (a.sc - pos) / 8);  // pieces
-            auto row = [&](int i, uint32_t z) BS_INL { return a.node[i] + uint64_t(z) * a.sc + pos; };
+            auto row = [&](int i, uint32_t z) BS_INL { return a.node[i] + uint64_t(z) * a.sc + ip; };
             uint32_t pl[Q][8];  // C_e planes of the line's layers (digit ye = x)
             sfor<Q>([&](auto kc) BS_INL {
                 constexpr int x = (XE + 1 + decltype(kc)::value) % Q;  // the red layer (x = xe) last
@@ -163,7 +177,7 @@ struct Dec1Kernel {
 #pragma unroll
                             for (int xx = 1; xx < Q; xx++) cn = d == xx ? a.node[yi * Q + xx] : cn;
                             const uint32_t zc = uint32_t(int(z) + (xi - d) * wt(yi));
-                            ld32<FULL, BT>(cv, cn + uint64_t(zc) * a.sc + pos, nv);
+                            ld32<FULL, BT>(cv, cn + uint64_t(zc) * a.sc + ip, nv);
                             const uint32_t keep = d != xi ? 0xffffffffu : 0u;
                             const uint32_t ks = keep & 0xfefefefeu, kr = keep & 0x1d1d1d1du;
 #pragma unroll
@@ -196,22 +210,34 @@ struct Dec1Kernel {
                     ob[w] = acc[w];
                 }
                 transpose8(ob);
-                st32<FULL, BT>(a.out + uint64_t(z) * a.sc + pos, ob, nv);
+                st32<FULL, BT>(a.out + uint64_t(z) * a.sc + op, ob, nv);
             });
         }
     }
 };
 
-template <int KD, int M, int E, int PG, bool BT = false>
+// BATCH: many stripes with the same erased node in one launch (Dec1Args ncols, cps, sin, sout).
+// Tiles are flattened over COLUMNS (32 positions of one stripe), not over one stripe's positions:
+// tile t owns columns [t * PG, +PG) of the nstripes * cps columns, so a 32-byte sub-chunk fills
+// the workgroup with PG stripes and tiles may straddle stripe boundaries.  A workgroup still
+// holds every line of each of its columns (the companion rows are read by its other lanes).
+template <int KD, int M, int E, int PG, bool BT = false, bool BATCH = false>
 __global__ __launch_bounds__((Dec1Kernel<KD, M, E, PG>::BLOCK)) void k_bs_decode1(Dec1Args a) {
     using Kn = Dec1Kernel<KD, M, E, PG>;
     const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
     for (uint32_t tix = slot; tix < a.tiles_per_xcd; tix += a.nslots) {
         const uint32_t tile = xcd * a.tiles_per_xcd + tix;  // each XCD streams a contiguous run
         if (tile >= a.ntiles) break;
-        const uint64_t b0 = uint64_t(tile) * Kn::W;
-        if (b0 + Kn::W <= a.sc) Kn::template tile<true, BT>(a, b0);
-        else Kn::template tile<false, BT>(a, b0);
+        if constexpr (BATCH) {
+            const uint64_t c0 = uint64_t(tile) * PG;
+            // every lane a whole column: sc a multiple of 32 and no column past the last stripe
+            if ((a.sc & 31u) == 0 && c0 + PG <= a.ncols) Kn::template tile<true, BT, true>(a, c0);
+            else Kn::template tile<false, BT, true>(a, c0);
+        } else {
+            const uint64_t b0 = uint64_t(tile) * Kn::W;
+            if (b0 + Kn::W <= a.sc) Kn::template tile<true, BT>(a, b0);
+            else Kn::template tile<false, BT>(a, b0);
+        }
     }
 }
 

@@ -1579,17 +1579,25 @@ struct Strided {
     int64_t pnode, pstripe;
 };
 
-static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const uint8_t *const *data,
-                                 uint8_t *const *par, size_t n_stripes, size_t chunk, hipStream_t stream,
-                                 const Strided *sd) {
+// Batches are launch-bound where a stripe is small: at least kBatchMinStripes stripes of at most
+// kBatchMaxStripeBytes of data (k x chunk) each run as a batch, anything else stripe by stripe.
+// Measured for the encode; the batched decode takes the same thresholds, which
+// nobody has measured for it (its single-launch line batch has no minimum stripe count).
+constexpr size_t kBatchMinStripes = 4;
+constexpr size_t kBatchMaxStripeBytes = size_t(4) << 20;
+
+// A cached plan (encode or decode: the executor only sees operand bases) over a batch of stripes:
+// one k_gexec launch per plan level for all of them.  `bases`: the plan's bound operand bases
+// (internal node indices); ptr_of(b, s): base b's pointer in stripe s.  `strided`: the pointers
+// are affine in s by construction (no scan).  *launches += the launches issued.
+template <class PtrOf>
+static Error run_plan_batch(CodeState &cs, DevState &ds, int dev, const Plan &pl, const std::vector<size_t> &bases,
+                            const PtrOf &ptr_of, bool strided, size_t n_stripes, size_t chunk, hipStream_t stream,
+                            size_t *launches_out) {
     const clay_code_t &c = cs.code;
     const uint32_t tn = uint32_t(c.q * c.t);
-    const Plan *plp = nullptr;
-    Error e = encode_plan(cs, &plp);
-    if (e) return e;
-    const Plan &pl = *plp;
     CodeState::DevGrouped g{};
-    e = upload_groups(cs, pl, dev, &g, stream);
+    Error e = upload_groups(cs, pl, dev, &g, stream);
     if (e) return e;
     const uint64_t sc = chunk / c.sub_chunk_no;
     const uint32_t lanes = uint32_t(sc / 16 + 1);  // 16-byte lanes incl. the byte tail
@@ -1609,27 +1617,19 @@ static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const uin
         ExecPtrs P{};
         ExecStride S{};
         bool affine = true;
-        auto affine_of = [&](size_t base, auto ptr_of) {
-            if (sd) {  // strided layout: affine by construction
-                P.p[base] = ptr_of(0);
-                S.s[base] = int64_t(ptr_of(1) - ptr_of(0));
-                return;
+        for (size_t bi = 0; bi < bases.size() && affine; bi++) {
+            const size_t base = bases[bi];
+            uint8_t *p0 = ptr_of(base, s0);
+            if (strided) {  // strided layout: affine by construction
+                P.p[base] = p0;
+                S.s[base] = int64_t(ptr_of(base, s0 + 1) - p0);
+                continue;
             }
-            uint8_t *p0 = ptr_of(0);
-            const int64_t st = ns > 1 ? int64_t(ptr_of(1) - p0) : 0;
-            for (size_t s = 2; s < ns && affine; s++) affine = ptr_of(s) == p0 + int64_t(s) * st;
+            const int64_t st = ns > 1 ? int64_t(ptr_of(base, s0 + 1) - p0) : 0;
+            for (size_t s = 2; s < ns && affine; s++) affine = ptr_of(base, s0 + s) == p0 + int64_t(s) * st;
             P.p[base] = p0;
             S.s[base] = st;
-        };
-        for (size_t i = 0; i < c.k && affine; i++)
-            affine_of(i, [&](size_t s) {
-                return sd ? const_cast<uint8_t *>(sd->data) + int64_t(s0 + s) * sd->dstripe + int64_t(i) * sd->dnode
-                          : const_cast<uint8_t *>(data[(s0 + s) * c.k + i]);
-            });
-        for (size_t i = 0; i < c.m && affine; i++)
-            affine_of(c.k + c.nu + i, [&](size_t s) {
-                return sd ? sd->par + int64_t(s0 + s) * sd->pstripe + int64_t(i) * sd->pnode : par[(s0 + s) * c.m + i];
-            });
+        }
         if (ws.l) {
             P.p[2 * tn] = ws.ptr();
             S.s[2 * tn] = int64_t(tn * chunk);
@@ -1640,8 +1640,7 @@ static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const uin
             std::vector<uint8_t *> tab(ns * kMaxBases, nullptr);
             for (size_t s = 0; s < ns; s++) {
                 uint8_t **t = &tab[s * kMaxBases];
-                for (size_t i = 0; i < c.k; i++) t[i] = const_cast<uint8_t *>(data[(s0 + s) * c.k + i]);
-                for (size_t i = 0; i < c.m; i++) t[c.k + c.nu + i] = par[(s0 + s) * c.m + i];
+                for (size_t base : bases) t[base] = ptr_of(base, s0 + s);
                 if (ws.l) t[2 * tn] = ws.ptr() + s * tn * chunk;
             }
             e = ptr_table(ds, tab, stream, &pt);
@@ -1664,6 +1663,30 @@ static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const uin
         e = ptu.done();
         if (e) return e;
     }
+    *launches_out += launches;
+    return Error{};
+}
+
+static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const uint8_t *const *data,
+                                 uint8_t *const *par, size_t n_stripes, size_t chunk, hipStream_t stream,
+                                 const Strided *sd) {
+    const clay_code_t &c = cs.code;
+    const Plan *plp = nullptr;
+    Error e = encode_plan(cs, &plp);
+    if (e) return e;
+    std::vector<size_t> bases;
+    for (size_t i = 0; i < c.k; i++) bases.push_back(i);
+    for (size_t i = 0; i < c.m; i++) bases.push_back(c.k + c.nu + i);
+    auto ptr_of = [&](size_t b, size_t s) -> uint8_t * {
+        if (b < c.k)
+            return sd ? const_cast<uint8_t *>(sd->data) + int64_t(s) * sd->dstripe + int64_t(b) * sd->dnode
+                      : const_cast<uint8_t *>(data[s * c.k + b]);
+        const size_t j = b - c.k - c.nu;
+        return sd ? sd->par + int64_t(s) * sd->pstripe + int64_t(j) * sd->pnode : par[s * c.m + j];
+    };
+    size_t launches = 0;
+    e = run_plan_batch(cs, ds, dev, *plp, bases, ptr_of, sd != nullptr, n_stripes, chunk, stream, &launches);
+    if (e) return e;
     t_last_launches += launches;
     t_last_path = "staged-batch";
     return Error{};
@@ -1798,7 +1821,7 @@ static Error encode_device_impl(const clay_code_t *code, const uint8_t *const *d
     // many small stripes: one launch for the whole batch instead of one per stripe
     // (launch-bound below ~4 MiB of data per stripe) -- the bit-sliced kernel where the
     // code has one and the stripes sit at uniform strides, else one launch per plan level
-    if (mode == kModeAuto && n_stripes >= 4 && code->k * chunk <= (size_t(4) << 20) &&
+    if (mode == kModeAuto && n_stripes >= kBatchMinStripes && code->k * chunk <= kBatchMaxStripeBytes &&
         code->q * code->t <= size_t(kMaxTn)) {
         bool done = false;
         e = encode_bs_batch(cs, dev, data, par, n_stripes, chunk, st, sd, &done);
@@ -2257,25 +2280,28 @@ static Error launch_bs_decode1(CodeState &cs, const DevProps &prop, const uint8_
     return Error{};
 }
 
-static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
-                                uint8_t *const *outs, size_t chunk, int dev, void *stream, bool codeword = false) {
-    Error e = check_code(code);
-    if (e) return e;
-    const clay_code_t &c = *code;
-    if (!chunks || !outs) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
+// Validation of a device decode, before any device work (decode.rs:36-126 with available = the
+// non-NULL entries of `chunks`): `erased` / `want` per internal node, *n_present = the available
+// chunks.  *nothing: no chunk and no erasure -- the call returns CLAY_OK at once.
+static Error decode_check(const clay_code_t &c, const uint8_t *const *chunks, const size_t *er, size_t ner,
+                          uint8_t *const *outs, size_t chunk, std::vector<uint8_t> &erased, std::vector<uint8_t> &want,
+                          size_t *n_present, bool *nothing) {
+    *nothing = false;
     std::vector<size_t> ids, lens;
     for (size_t i = 0; i < c.n; i++)
         if (chunks[i]) {
             ids.push_back(i);
             lens.push_back(chunk);
         }
-    if (ids.empty() && ner == 0) return Error{};
+    *n_present = ids.size();
+    if (ids.empty() && ner == 0) {
+        *nothing = true;
+        return Error{};
+    }
     size_t cs_sz = 0;
-    std::vector<uint8_t> erased;
-    e = validate_decode(c, AvailView{ids.data(), lens.data(), ids.size()}, er, ner, &cs_sz, erased);
+    Error e = validate_decode(c, AvailView{ids.data(), lens.data(), ids.size()}, er, ner, &cs_sz, erased);
     if (e) return e;
-    const size_t tn = c.q * c.t;
-    std::vector<uint8_t> want(tn, 0);
+    want.assign(c.q * c.t, 0);
     for (size_t i = 0; i < ner; i++) {
         size_t in = internal_of(c, er[i]);
         if (er[i] < c.k && !outs[er[i]])
@@ -2283,6 +2309,21 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
                               er[i]);
         want[in] = outs[er[i]] ? 1 : 0;
     }
+    return Error{};
+}
+
+static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
+                                uint8_t *const *outs, size_t chunk, int dev, void *stream, bool codeword = false) {
+    Error e = check_code(code);
+    if (e) return e;
+    const clay_code_t &c = *code;
+    if (!chunks || !outs) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
+    std::vector<uint8_t> erased, want;
+    size_t n_present = 0;
+    bool nothing = false;
+    e = decode_check(c, chunks, er, ner, outs, chunk, erased, want, &n_present, &nothing);
+    if (e || nothing) return e;
+    const size_t tn = c.q * c.t;
     t_last_launches = 0;
     DevState *ds;
     e = dev_state(dev, &ds);
@@ -2309,13 +2350,13 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
     // codeword): a single erasure is rebuilt by the repair kernel under the exec modes that pick
     // the bit-sliced repair kernels (auto, "stream": as repair_device_impl); every other decode,
     // and every decode under "grouped" / "tile" (A/B runs), runs as clay_decode_device does
-    if (codeword && (xmode == kExecAuto || xmode == kExecStream) && n_erased == 1 && ner == 1 && ids.size() + 1 == c.n) {
+    if (codeword && (xmode == kExecAuto || xmode == kExecStream) && n_erased == 1 && ner == 1 && n_present + 1 == c.n) {
         bool done = false;
         e = decode_by_repair(c, chunks, er[0], outs[er[0]], chunk, dev, static_cast<hipStream_t>(stream), &done);
         if (e || done) return e;
     }
     // one erasure of (4,2,5) with every other chunk present: the bit-sliced single-erasure decode
-    if ((xmode == kExecAuto || xmode == kExecStream) && n_erased == 1 && ner == 1 && ids.size() + 1 == c.n) {
+    if ((xmode == kExecAuto || xmode == kExecStream) && n_erased == 1 && ner == 1 && n_present + 1 == c.n) {
         bool done = false;
         e = launch_bs_decode1(cs, dev_props(dev), chunks, er[0], outs[er[0]], chunk, static_cast<hipStream_t>(stream),
                               &done);
@@ -2373,6 +2414,185 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
         }
     }
     return run_plan(cs, *plan, dev, *ds, static_cast<hipStream_t>(stream), P, chunk / c.sub_chunk_no, chunk);
+}
+
+// ---- batched decode: n_stripes stripes with the same erasure set (clay_decode_device_strided /
+// clay_decode_device_batch) ----
+// Stripes at fixed strides: node i of stripe s at chunks + s * stripe + i * node, the rebuilt
+// node e at out + s * ostripe + e * onode.
+struct DecStrided {
+    const uint8_t *chunks;
+    int64_t node, stripe;
+    uint8_t *out;
+    int64_t onode, ostripe;
+};
+
+// Line batch: one erasure of (4,2,5) in every stripe, stripe s = stripe 0's pointers + s * sin
+// (inputs) / s * sout (output): ONE launch of the column-flattened k_bs_decode1 (bitslice_line.hpp)
+// at any sub-chunk size and alignment.  No allocation, no pointer table: capturable unprepared.
+static Error launch_bs_decode1_batch(CodeState &cs, const DevProps &prop, const uint8_t *const *chunks0, int64_t sin,
+                                     size_t e, uint8_t *out0, int64_t sout, size_t ns, size_t chunk,
+                                     hipStream_t stream, bool *done) {
+    *done = false;
+    const clay_code_t &c = cs.code;
+    const int W = bs_decode1_tile(int(c.k), int(c.m));
+    if (!W || c.d != c.k + c.m - 1 || c.nu != 0 || !out0 || c.q * c.t > 8) return Error{};
+    const size_t sc = chunk / c.sub_chunk_no;
+    if (sc == 0 || chunk % c.sub_chunk_no) return Error{};
+    using S = bs::Shape<4, 2>;  // the only instantiation (bs_decode1_tile)
+    for (int p = 0; p < 2; p++)
+        for (int i = 0; i < S::K; i++)
+            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
+                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    const uint64_t cps = (uint64_t(sc) + 31) / 32, pg = uint64_t(W) / 32;
+    if (cps >= 0xFFFFFFFFull || ns >= 0xFFFFFFFFull || cps * ns >= 0xFFFFFFFFull) return Error{};  // 32-bit columns
+    bs::Dec1Args a{};
+    bool bt = sc % 8 != 0 || (reinterpret_cast<uintptr_t>(out0) & 7u) != 0 || (sin & 7) != 0 || (sout & 7) != 0;
+    for (size_t i = 0; i < c.n; i++) {
+        if (i == e) continue;
+        if (!chunks0[i]) return Error{};
+        a.node[internal_of(c, i)] = chunks0[i];
+        bt |= (reinterpret_cast<uintptr_t>(chunks0[i]) & 7u) != 0;
+    }
+    a.out = out0;
+    a.sc = sc;
+    a.cps = uint32_t(cps);
+    a.ncols = uint32_t(cps * ns);
+    a.sin = sin;
+    a.sout = sout;
+    a.ntiles = uint32_t((cps * ns + pg - 1) / pg);
+    a.tiles_per_xcd = (a.ntiles + 7) / 8;
+    a.nslots = std::min(a.tiles_per_xcd, uint32_t(std::max(1, prop.cus / 8) * 8));
+    CLAY_HIP(launch_bs_decode1_kernel(int(c.k), int(c.m), int(internal_of(c, e)), bt, a, stream, true));
+    t_last_launches += 1;
+    t_last_exec = "bs-decode1-batch";
+    *done = true;
+    return Error{};
+}
+
+// chunks / outs: n_stripes x n pointer arrays (sd == nullptr), or the strided layout `sd`.
+static Error decode_batch_impl(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
+                               uint8_t *const *outs, size_t n_stripes, size_t chunk, int dev, void *stream,
+                               const DecStrided *sd) {
+    Error e = check_code(code);
+    if (e) return e;
+    const clay_code_t &c = *code;
+    if (sd ? (!sd->chunks || !sd->out) : (!chunks || !outs))
+        return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
+    if (ner && !er) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null erasure array");
+    if (!sd && n_stripes == 0) return Error{};  // no stripe to take the NULL pattern from
+    // stripe 0's pointer arrays: the strided form has every node outside `erasures` available and
+    // rebuilds every erased one
+    std::vector<const uint8_t *> c0(c.n, nullptr);
+    std::vector<uint8_t *> o0(c.n, nullptr);
+    std::vector<uint8_t> gone(c.n, 0);
+    if (sd)
+        for (size_t i = 0; i < ner; i++)
+            if (er[i] < c.n) gone[er[i]] = 1;
+    auto cptr = [&](size_t s, size_t i) -> const uint8_t * {
+        if (!sd) return chunks[s * c.n + i];
+        return gone[i] ? nullptr : sd->chunks + int64_t(s) * sd->stripe + int64_t(i) * sd->node;
+    };
+    auto optr = [&](size_t s, size_t i) -> uint8_t * {
+        if (!sd) return outs[s * c.n + i];
+        return gone[i] ? sd->out + int64_t(s) * sd->ostripe + int64_t(i) * sd->onode : nullptr;
+    };
+    for (size_t i = 0; i < c.n; i++) {
+        c0[i] = cptr(0, i);
+        o0[i] = optr(0, i);
+    }
+    std::vector<uint8_t> erased, want;
+    size_t n_present = 0;
+    bool nothing = false;
+    e = decode_check(c, c0.data(), er, ner, o0.data(), chunk, erased, want, &n_present, &nothing);
+    if (e || nothing) return e;
+    if (!sd)
+        for (size_t s = 1; s < n_stripes; s++)
+            for (size_t i = 0; i < c.n; i++)
+                if (!chunks[s * c.n + i] != !c0[i] || (!c0[i] && !outs[s * c.n + i] != !o0[i]))
+                    return make_error(CLAY_ERR_INVALID_PARAMETERS, s, i, 0,
+                                      "Invalid parameters: stripe %zu differs from stripe 0 in the NULL pattern at node %zu",
+                                      s, i);
+    if (n_stripes == 0) return Error{};
+    const size_t tn = c.q * c.t;
+    t_last_launches = 0;
+    DevState *ds;
+    e = dev_state(dev, &ds);
+    if (e) return e;
+    DeviceGuard g(dev);
+    CodeState &cs = *code_state(c);
+    if (tn > size_t(kMaxTn))
+        return make_error(CLAY_ERR_DEVICE, tn, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int xmode = g_exec_mode.load(std::memory_order_relaxed);
+    if (c.k * chunk <= kBatchMaxStripeBytes) {
+        size_t n_erased = 0;
+        for (size_t in = 0; in < tn; in++) n_erased += erased[in] && !(in >= c.k && in < c.k + c.nu) ? 1 : 0;
+        // line batch: one erasure of (4,2,5), every other chunk present, auto / "stream", the
+        // stripes at uniform strides (the strided form, or pointer arrays that are rows of one
+        // buffer); one launch for any number of stripes
+        if ((xmode == kExecAuto || xmode == kExecStream) && n_erased == 1 && ner == 1 && n_present + 1 == c.n &&
+            bs_decode1_tile(int(c.k), int(c.m)) && o0[er[0]]) {
+            const size_t i0 = er[0] == 0 ? 1 : 0;  // a present node
+            const int64_t sin = sd ? sd->stripe : n_stripes > 1 ? int64_t(cptr(1, i0) - c0[i0]) : 0;
+            const int64_t sout = sd ? sd->ostripe : n_stripes > 1 ? int64_t(optr(1, er[0]) - o0[er[0]]) : 0;
+            bool uniform = true;
+            if (!sd)
+                for (size_t s = 1; s < n_stripes && uniform; s++) {
+                    for (size_t i = 0; i < c.n && uniform; i++)
+                        if (c0[i]) uniform = cptr(s, i) == c0[i] + int64_t(s) * sin;
+                    uniform = uniform && optr(s, er[0]) == o0[er[0]] + int64_t(s) * sout;
+                }
+            if (uniform) {
+                bool done = false;
+                e = launch_bs_decode1_batch(cs, dev_props(dev), c0.data(), sin, er[0], o0[er[0]], sout, n_stripes, chunk,
+                                            st, &done);
+                if (e || done) return e;
+            }
+        }
+    }
+    if (n_stripes >= kBatchMinStripes && c.k * chunk <= kBatchMaxStripeBytes) {
+        // staged batch: the cached decode plan, one k_gexec launch per level for the whole batch
+        std::vector<uint8_t> key(erased);
+        key.insert(key.end(), want.begin(), want.end());
+        const Plan *plan = nullptr;
+        e = cached_plan(cs, cs.dec, key, [&](std::unique_ptr<Plan> &p) { return plan_decode(c, cs.rs, erased, want, p); },
+                        &plan);
+        if (e) return e;
+        std::vector<size_t> bases, ext(tn, 0);
+        for (size_t i = 0; i < c.n; i++) {
+            const size_t in = internal_of(c, i);
+            if (c0[i] || (want[in] && o0[i])) {
+                bases.push_back(in);
+                ext[in] = i;
+            }
+        }
+        auto ptr_of = [&](size_t b, size_t s) -> uint8_t * {
+            const size_t i = ext[b];
+            return c0[i] ? const_cast<uint8_t *>(cptr(s, i)) : optr(s, i);
+        };
+        size_t launches = 0;
+        e = run_plan_batch(cs, *ds, dev, *plan, bases, ptr_of, sd != nullptr, n_stripes, chunk, st, &launches);
+        if (e) return e;
+        t_last_launches += launches;
+        t_last_exec = "grouped-batch";
+        return Error{};
+    }
+    // few or large stripes: stripe by stripe
+    std::vector<const uint8_t *> cv(c.n);
+    std::vector<uint8_t *> ov(c.n);
+    size_t launches = 0;
+    for (size_t s = 0; s < n_stripes; s++) {
+        for (size_t i = 0; i < c.n; i++) {
+            cv[i] = cptr(s, i);
+            ov[i] = optr(s, i);
+        }
+        e = decode_device_impl(code, cv.data(), er, ner, ov.data(), chunk, dev, stream);
+        if (e) return e;
+        launches += t_last_launches;
+    }
+    t_last_launches = launches;
+    return Error{};
 }
 
 static Error repair_device_impl(const clay_code_t *code, size_t lost, const size_t *ids, const uint8_t *const *bufs,
@@ -2747,6 +2967,24 @@ int clay_decode_device_codeword(const clay_code_t *code, const uint8_t *const *c
                                 uint8_t *const *outs, size_t chunk, int device, void *stream, clay_error_t *err) {
     if (err) std::memset(err, 0, sizeof(*err));
     Error e = decode_device_impl(code, chunks, er, ner, outs, chunk, device, stream, true);
+    return e ? report(e, err) : 0;
+}
+
+int clay_decode_device_strided(const clay_code_t *code, const uint8_t *chunks, int64_t node_stride,
+                               int64_t stripe_stride, const size_t *er, size_t ner, uint8_t *out,
+                               int64_t out_node_stride, int64_t out_stripe_stride, size_t ns, size_t chunk, int device,
+                               void *stream, clay_error_t *err) {
+    if (err) std::memset(err, 0, sizeof(*err));
+    const DecStrided sd{chunks, node_stride, stripe_stride, out, out_node_stride, out_stripe_stride};
+    Error e = decode_batch_impl(code, nullptr, er, ner, nullptr, ns, chunk, device, stream, &sd);
+    return e ? report(e, err) : 0;
+}
+
+int clay_decode_device_batch(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
+                             uint8_t *const *outs, size_t ns, size_t chunk, int device, void *stream,
+                             clay_error_t *err) {
+    if (err) std::memset(err, 0, sizeof(*err));
+    Error e = decode_batch_impl(code, chunks, er, ner, outs, ns, chunk, device, stream, nullptr);
     return e ? report(e, err) : 0;
 }
 

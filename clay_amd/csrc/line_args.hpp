@@ -13,6 +13,12 @@ struct Dec1Args {
     uint8_t *out;            // the erased node's chunk
     uint64_t sc;             // sub-chunk bytes
     uint32_t ntiles, tiles_per_xcd, nslots;
+    // batches (the BATCH instantiations only): stripe s's nodes at node[i] + s * sin, its output
+    // at out + s * sout.  A column is 32 positions of one stripe, cps = ceil(sc / 32) columns per
+    // stripe, ncols = nstripes * cps columns in all (< 2^32); tile t owns columns [t * PG, +PG),
+    // ntiles / tiles_per_xcd count those tiles.
+    uint32_t ncols, cps;
+    int64_t sin, sout;
 };
 
 struct Enc1Args {
@@ -32,8 +38,10 @@ struct Enc1Args {
 // instantiation
 hipError_t launch_bs_encode1_kernel(int k, int m, bool bt, const bs::Enc1Args &a, hipStream_t stream);
 // line_kernels.hip: k_bs_decode1 for code (k, m) and erased internal node e; bt = byte tails
-// (unaligned chunks or sc % 8 != 0).  hipErrorInvalidValue: no instantiation
-hipError_t launch_bs_decode1_kernel(int k, int m, int e, bool bt, const bs::Dec1Args &a, hipStream_t stream);
+// (unaligned chunks or sc % 8 != 0); batch: the column-flattened instantiation (Dec1Args ncols,
+// cps, sin, sout).  hipErrorInvalidValue: no instantiation
+hipError_t launch_bs_decode1_kernel(int k, int m, int e, bool bt, const bs::Dec1Args &a, hipStream_t stream,
+                                    bool batch = false);
 // positions per tile and threads per workgroup of that instantiation (0: none)
 int bs_decode1_tile(int k, int m);
 

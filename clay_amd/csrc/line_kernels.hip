@@ -1,5 +1,6 @@
 // line_kernels.hip -- instantiations and launchers of the line-local bit-sliced kernels
-// (bitslice_line.hpp) for (4,2,5): the encode and the single-erasure decode of every node.
+// (bitslice_line.hpp) for (4,2,5): the encode and the single-erasure decode of every node (one
+// stripe, and the column-flattened batch of many stripes).
 #include "bitslice_line.hpp"
 
 namespace clay {
@@ -9,22 +10,26 @@ constexpr int kPg = 64;  // 32-position groups per tile: 2048 positions, 4 lines
 }
 
 template <int E>
-static hipError_t launch42(bool bt, const bs::Dec1Args &a, hipStream_t stream) {
+static hipError_t launch42(bool bt, const bs::Dec1Args &a, hipStream_t stream, bool batch) {
     using Kn = bs::Dec1Kernel<4, 2, E, kPg>;
-    if (bt) bs::k_bs_decode1<4, 2, E, kPg, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
+    if (batch) {
+        if (bt) bs::k_bs_decode1<4, 2, E, kPg, true, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
+        else bs::k_bs_decode1<4, 2, E, kPg, false, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
+    } else if (bt) bs::k_bs_decode1<4, 2, E, kPg, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
     else bs::k_bs_decode1<4, 2, E, kPg><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
     return hipGetLastError();
 }
 
-hipError_t launch_bs_decode1_kernel(int k, int m, int e, bool bt, const bs::Dec1Args &a, hipStream_t stream) {
+hipError_t launch_bs_decode1_kernel(int k, int m, int e, bool bt, const bs::Dec1Args &a, hipStream_t stream,
+                                    bool batch) {
     if (k == 4 && m == 2) {
         switch (e) {
-        case 0: return launch42<0>(bt, a, stream);
-        case 1: return launch42<1>(bt, a, stream);
-        case 2: return launch42<2>(bt, a, stream);
-        case 3: return launch42<3>(bt, a, stream);
-        case 4: return launch42<4>(bt, a, stream);
-        case 5: return launch42<5>(bt, a, stream);
+        case 0: return launch42<0>(bt, a, stream, batch);
+        case 1: return launch42<1>(bt, a, stream, batch);
+        case 2: return launch42<2>(bt, a, stream, batch);
+        case 3: return launch42<3>(bt, a, stream, batch);
+        case 4: return launch42<4>(bt, a, stream, batch);
+        case 5: return launch42<5>(bt, a, stream, batch);
         default: break;
         }
     }

@@ -209,6 +209,41 @@ int clay_decode_device_codeword(const clay_code_t *code, const uint8_t *const *c
                                 const size_t *erasures, size_t n_erasures, uint8_t *const *out_chunks,
                                 size_t chunk_size, int device, void *stream, clay_error_t *err);
 
+/* Batched decode of n_stripes stripes with the SAME erasure set, laid out at fixed strides in
+ * device memory (the reference decodes one stripe per call, decode.rs:31-161; its benchmark,
+ * benches/clay_bench.rs:58-93, decodes 1 KiB - 1 MiB stripes, which are launch-bound on a GPU;
+ * after a node failure every stripe has the same erasure pattern).  Node i (external index,
+ * 0..n-1) of stripe s is at chunks + s*stripe_stride + i*node_stride; the slots of erased nodes are
+ * never read.  Every node not listed in `erasures` is available.  Every erased node e (data or
+ * parity) of stripe s is rebuilt at out + s*out_stripe_stride + e*out_node_stride.  out may equal
+ * chunks with the same strides (rebuild in place into the erased slots); otherwise output regions
+ * must not overlap any region that is read.  Validation runs once, before any device work, exactly
+ * as clay_decode_device's (decode.rs:36-126); n_stripes == 0 returns CLAY_OK and launches nothing.
+ * Each stripe's output bytes are those of clay_decode_device for that stripe alone, on any input.
+ * Paths (clay_set_exec_mode): stripes of <= 4 MiB of data each run as a batch -- (4,2,5) with one
+ * erasure as ONE launch of the batched k_bs_decode1 for any number of stripes (last exec path
+ * "bs-decode1-batch", any sub-chunk size and alignment; allocates nothing, so it may be captured
+ * unprepared), anything else, from 4 stripes, as one k_gexec launch per level of the decode plan
+ * ("grouped-batch"; inside a stream capture it must have been prepared by one call of the same
+ * shape, like clay_decode_device); fewer or larger stripes run stripe by stripe as
+ * clay_decode_device.  Asynchronous on `stream`. */
+int clay_decode_device_strided(const clay_code_t *code, const uint8_t *chunks, int64_t node_stride,
+                               int64_t stripe_stride, const size_t *erasures, size_t n_erasures,
+                               uint8_t *out, int64_t out_node_stride, int64_t out_stripe_stride,
+                               size_t n_stripes, size_t chunk_size, int device, void *stream,
+                               clay_error_t *err);
+
+/* Pointer-array form of clay_decode_device_strided (decode.rs:31-161 per stripe; the stripe sizes
+ * of benches/clay_bench.rs:58-93): stripe s uses chunks[s*n .. s*n+n) and
+ * out_chunks[s*n .. s*n+n) with the NULL conventions of clay_decode_device; the NULL pattern must
+ * be identical in every stripe (else CLAY_ERR_INVALID_PARAMETERS).  Pointer arrays that are rows of
+ * one buffer (uniform stripe strides) take the same paths as the strided form; others run the
+ * batch through a cached device pointer table ("grouped-batch"). */
+int clay_decode_device_batch(const clay_code_t *code, const uint8_t *const *chunks,
+                             const size_t *erasures, size_t n_erasures, uint8_t *const *out_chunks,
+                             size_t n_stripes, size_t chunk_size, int device, void *stream,
+                             clay_error_t *err);
+
 /* Repair on device: helper buffers are device pointers (beta*sub-chunk bytes),
  * out is a device buffer of chunk_size bytes. */
 int clay_repair_device(const clay_code_t *code, size_t lost_node, const size_t *helper_ids,
@@ -302,9 +337,16 @@ int clay_set_encode_path(int mode);
  *                y-section (sc % 8 == 0; the BASELINE {0,4,8,12} and the (2,1,1) / (2,2)
  *                patterns included) the fused decode v2 (k_stream_fused2, "stream-fused2");
  *                (4,2,5) with one erasure and every other chunk present: the single-erasure
- *                bit-sliced decode (k_bs_decode1, "bs-decode1", any sub-chunk and alignment)
- *   1 grouped -- always the grouped executor (k_gexec, one launch per level)
- *   2 tile    -- the tile executor wherever its U slots fit, whatever the plan size
+ *                bit-sliced decode (k_bs_decode1, "bs-decode1", any sub-chunk and alignment);
+ *                batched decodes (clay_decode_device_strided / _batch, stripes of <= 4 MiB of
+ *                data): (4,2,5) with one erasure at uniform stripe strides in one launch of
+ *                the batched k_bs_decode1 ("bs-decode1-batch"), every other code, pattern or
+ *                layout, from 4 stripes, one k_gexec launch per plan level for the whole batch
+ *                ("grouped-batch")
+ *   1 grouped -- always the grouped executor (k_gexec, one launch per level); batched decodes
+ *                always "grouped-batch" (the A/B partner of the line batch)
+ *   2 tile    -- the tile executor wherever its U slots fit, whatever the plan size; batched
+ *                decodes as under grouped ("grouped-batch": the tile executor has no batch form)
  *   (auto and stream: repair of (9,3,11), (10,4,13), (4,2,5) from all n - 1 other nodes runs
  *    the bit-sliced repair kernels: k_bs_repair_stream (LDS-DMA streaming, one workgroup per
  *    CU; auto when the sub-chunk gives every CU a tile, stream for any sub-chunk >= 16 bytes
@@ -330,7 +372,8 @@ int clay_set_exec_mode(int mode);
  * "tile" (k_texec), "grouped" (k_gexec), "stream-local256" (k_stream_local256), "stream-local"
  * (k_stream_local), "stream-fused2"
  * (k_stream_fused2), "bs-decode1" (k_bs_decode1), "bs-repair-stream" (k_bs_repair_stream),
- * "bs-repair" (k_bs_repair) or "none". */
+ * "bs-repair" (k_bs_repair), the batched decodes' "bs-decode1-batch" (k_bs_decode1 over many
+ * stripes) and "grouped-batch" (k_gexec over many stripes), or "none". */
 const char *clay_last_exec_path(void);
 
 /* Name of the path the last encode on this thread used ("fused-q4w128p8", "staged", ...). */

@@ -120,6 +120,81 @@ def _decode_cfg(k, m, d, stripe, er, codeword=False):
                {"writes_counted": "erased data nodes only"})
 
 
+def timed_alternating(fns):
+    """timed() for several variants with their samples interleaved (A B A B ...), so clock and
+    box drift hit all of them alike.  fns: callables; returns [(median, min)] in their order."""
+    ts = [[] for _ in fns]
+    for i in range(RUNS + 2):
+        for j, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fn()
+            e0.record(stream)
+            for _ in range(B2B):
+                fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if i >= 2:
+                ts[j].append(e0.elapsed_time(e1) / B2B)
+    return [(float(np.median(t)), float(np.min(t))) for t in ts]
+
+
+def decode_batch_cfg(k, m, d, stripe, n, e, loop_stripes):
+    """clay_bench.rs stripe sizes, one lost node in every stripe, about 64 MiB of input per call:
+    clay_decode_device_strided under auto (the line batch for (4,2,5)) and under "grouped" (the
+    staged batch), samples alternated; then the only way without a batch entry point, a loop of
+    per-stripe clay_decode_device calls on the same buffers (the first loop_stripes stripes,
+    reported per stripe; host and launch overhead included: that is what the caller pays).
+    Bytes: what the algorithm moves per stripe -- the line kernel reads 4.5 chunks (half of the
+    ignored node) and writes 1, not 5 + 1."""
+    c = ClayCode(k, m, d)
+    chunk = c.encoded_chunk_size(stripe)
+    full = rnd(n * c.n, chunk, 6).view(n, c.n, chunk)
+    outs = torch.empty((n, c.n, chunk), dtype=torch.uint8, device="cuda")
+    algo = int(n * 5.5 * chunk)
+    name = f"decode ({k},{m},{d}) batch {n} x {stripe >> 10} KiB erasure [{e}]"
+
+    def call(mode):
+        def fn():
+            clay_amd.set_exec_mode(mode)
+            c.decode_device_strided(full, [e], outs, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+        return fn
+
+    prev = clay_amd.set_exec_mode("auto")
+    try:
+        modes = ("auto", "grouped")
+        res = timed_alternating([call(mo) for mo in modes])
+        for mo, (ms, mn) in zip(modes, res):
+            call(mo)()
+            torch.cuda.synchronize()
+            report(f"{name} {mo}", ms, mn, algo,
+                   {"bytes_counted": "per stripe 4.5 chunks read + 1 written", "per_stripe_us": round(ms * 1e3 / n, 6),
+                    "stripe_data_GiBps": round(n * k * chunk / (ms * 1e-3) / 2**30, 1)})
+        clay_amd.set_exec_mode("auto")
+        nl = min(n, loop_stripes)
+        ins = [[None if i == e else full[s, i] for i in range(c.n)] for s in range(nl)]
+        ous = [[outs[s, i] if i == e else None for i in range(c.n)] for s in range(nl)]
+
+        def loop():
+            for s in range(nl):
+                c.decode_device(ins[s], [e], ous[s], chunk, 0, stream.cuda_stream)
+
+        ts = []
+        for i in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            loop()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if i >= 1:
+                ts.append(e0.elapsed_time(e1))
+        ms, mn = float(np.median(ts)), float(np.min(ts))
+        report(f"{name} per-stripe loop of {nl}", ms, mn, int(nl * 5.5 * chunk),
+               {"bytes_counted": "per stripe 4.5 chunks read + 1 written", "per_stripe_us": round(ms * 1e3 / nl, 4),
+                "stripe_data_GiBps": round(nl * k * chunk / (ms * 1e-3) / 2**30, 1)})
+    finally:
+        clay_amd.set_exec_mode(prev)
+
+
 def repair_cfg(k, m, d, chunk, lost):
     c = ClayCode(k, m, d)
     sc = chunk // c.sub_chunk_no
@@ -160,6 +235,11 @@ if __name__ == "__main__":
             ("encode", lambda: encode_cfg(4, 2, 5, 64 << 20)),
             ("encode", lambda: encode_cfg(9, 3, 11, 9 * (256 << 20))),
             ("batch", lambda: encode_batch_cfg(4, 2, 5, 1 << 20, 256)),
+            # the clay_bench.rs stripe sizes with node 0 lost in every stripe, ~64 MiB per call
+            ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 1 << 10, 65536, 0, 1024)),
+            ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 10 << 10, 6553, 0, 1024)),
+            ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 100 << 10, 655, 0, 655)),
+            ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 1 << 20, 64, 0, 64)),
             ("decode", lambda: decode_cfg(4, 2, 5, 64 << 20, [0])),
             ("decode", lambda: decode_cfg(10, 4, 13, 1 << 30, [0, 4, 8, 12])),
             ("decode", lambda: decode_cfg(10, 4, 13, 1 << 30, [0, 4, 8, 12], "grouped")),
