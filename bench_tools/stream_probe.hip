@@ -258,6 +258,39 @@ int main(int argc, char **argv) {
         }
         return 0;
     }
+    if (argc > 2 && argv[2][0] == 'r') {  // tile map A/B: BalancedMap (the library's) vs StreamMap (PROBE 2097152)
+        // library kernel: 4 loaders, lane map kStreamEncMap.  Bytes first (the old map's are the
+        // parity-tested parent's), then full / memory only / live math only under both maps.
+        constexpr int M = kStreamEncMap, OLD = 2097152;
+        printf("sc %u tile map A/B (balanced rounds vs full rounds + narrow tail), back-to-back (200 launches after 50 untimed)\n", sc);
+        const size_t pbytes = 4 * chunk;
+        std::vector<uint8_t> ref(pbytes), got(pbytes);
+        (void)hipMemset(par, 0, pbytes);
+        run_b2b<4, OLD, M>(a, 1, 0);
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(ref.data(), par, pbytes, hipMemcpyDeviceToHost);
+        (void)hipMemset(par, 0xA5, pbytes);
+        run_b2b<4, 0, M>(a, 1, 0);
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(got.data(), par, pbytes, hipMemcpyDeviceToHost);
+        printf("  bytes new == old: %s\n", ref == got ? "yes" : "NO");
+        (void)hipMemset(par, 0x5A, pbytes);
+        run_b2b<4, 4194304, M>(a, 1, 0);
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(got.data(), par, pbytes, hipMemcpyDeviceToHost);
+        printf("  bytes new, masked loads (PROBE 4194304) == old: %s\n", ref == got ? "yes" : "NO");
+        for (int rr = 0; rr < 3; rr++) {
+            rep("b2b full, old map", run_b2b<4, OLD, M>(a, 200));
+            rep("b2b full, balanced map", run_b2b<4, 0, M>(a, 200));
+            rep("b2b memory only, old map", run_b2b<4, OLD | 1, M>(a, 200));
+            rep("b2b memory only, balanced map", run_b2b<4, 1, M>(a, 200));
+            rep("b2b live math only, old map", run_b2b<4, OLD | 262146, M>(a, 200));
+            rep("b2b live math only, balanced map", run_b2b<4, 262146, M>(a, 200));
+            rep("b2b full, balanced map, masked loads", run_b2b<4, 4194304, M>(a, 200));
+            rep("b2b memory only, balanced, masked loads", run_b2b<4, 4194304 | 1, M>(a, 200));
+        }
+        return 0;
+    }
     if (argc > 2 && argv[2][0] == 'w') {  // the 'v' variants, 10 launches each (for one rocprofv3 --pmc pass)
         rep("full", run_b2b<4, 0>(a, 10, 2));
         rep("memory only", run_b2b<4, 1>(a, 10, 2));

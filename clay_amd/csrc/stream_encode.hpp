@@ -27,17 +27,22 @@
 //  * A lane's 32 positions are bytes [16p, 16p+16) and [128+16p, 128+16p+16) of the tile
 //    (p = part); at the parity stores neighbouring columns swap halves (DPP), so each
 //    16-byte store instruction of a wave writes 4 whole 256-byte row runs.
-//  * Tiles: every XCD owns a contiguous byte region of the sub-chunks; its workgroups
-//    take full tiles round robin (adjacent workgroups stream adjacent 256-byte runs of the
-//    same rows), and the remainder is cut into one partial tile per workgroup, always its
-//    last (bench_tools/ring_probe: XCD-blocked order streams 17 % faster than a global
-//    round robin and 25 % faster than one contiguous range per workgroup).
+//  * Tiles: every XCD owns a contiguous byte region of the sub-chunks; its workgroups cover
+//    it in rounds of adjacent tiles (adjacent workgroups stream adjacent runs of the same
+//    rows), the fewest rounds 256-byte tiles allow, of near-equal widths (multiples of 16,
+//    at most 16 apart: BalancedMap, stream_tile_map.hpp), so no pass is a narrow tile with
+//    a full tile's math (bench_tools/ring_probe: XCD-blocked order streams 17 % faster than
+//    a global round robin and 25 % faster than one contiguous range per workgroup).
+//    A tile narrower than 256 loads with clamped piece addresses (issue) and stores in the
+//    same DPP pairs as a full one with the lanes past its end masked off (put); only the
+//    tile holding a row end that is not a multiple of 16 is patched and stored plainly.
 //
 // Same linear map as the reference (decode_layered with erased = parity, decode.rs:167-257),
 // so the bytes are identical to the oracle's.
 #pragma once
 
 #include "encode_math.hpp"
+#include "stream_tile_map.hpp"  // StreamTile, BalancedMap
 
 namespace clay {
 namespace bs {
@@ -49,10 +54,22 @@ __device__ __forceinline__ const uint8_t *uniform_ptr(const uint8_t *p) {
     return reinterpret_cast<const uint8_t *>((uint64_t(hi) << 32) | lo);
 }
 
-struct StreamTile {
-    uint32_t b0, vend;  // positions [b0, b0 + 256) of every row, valid below vend
-};
+// LDS-DMA of the lanes in `mask` only (probe builds, StreamEnc LPRED): EXEC is set inside the
+// statement, so it is one VMEM instruction whatever the mask holds; a masked lane's LDS slot keeps
+// its bytes.  The two EXEC moves stand in for the s_nop between the M0 write and the DMA.
+__device__ __forceinline__ void dma16_masked(uint32_t lds_addr, const uint8_t *sbase, uint32_t voff, uint64_t mask) {
+    unsigned keep;
+    uint64_t ex;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_mov_b64 %1, exec\n\ts_mov_b64 exec, %5\n\t"
+        "global_load_lds_dwordx4 %3, %4\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep), "=&s"(ex)
+        : "s"(lds_addr), "v"(voff), "s"(sbase), "s"(mask)
+        : "memory");
+}
 
+// (k_stream_encode's own tile map is BalancedMap, stream_tile_map.hpp; StreamMap serves the other
+// streaming kernels and the probe's old-map builds, PROBE 2097152)
 // XCD x owns bytes [x * region, min((x + 1) * region, sc)); full W-byte tiles round robin over
 // the XCD's ns workgroups, the remainder one partial tile per workgroup (its last), so every
 // workgroup of an XCD streams the same number of bytes to within 32.
@@ -106,8 +123,10 @@ struct ChipMap {
 // MAP: compute-lane map (0: column c = 8 * wave + (lane >> 3), round 5; 1: the round-6 map below,
 // digit 2 of c per wave so that section 2's work is wave-uniform, the light waves 4-7; 2: the same
 // with the light waves 0-3, for A/B)
+// LPRED (probe builds only): a tile narrower than 256 whose width is a multiple of 16 loads with
+// the lanes past its end masked off (dma16_masked) instead of with clamped addresses
 template <int KD, int LOADERS, int CPL = 0, int CPS = 0, bool CSE = true, bool SINK = false, bool CHECK = false,
-          int MAP = 0>
+          int MAP = 0, bool LPRED = false>
 struct StreamEnc {
     using K6 = EncMath<KD>;
     using S = typename K6::S;
@@ -232,6 +251,14 @@ struct StreamEnc {
                     const uint8_t *base = uniform_ptr(a.data[node] + (uint64_t(g) * sc + t.b0));
 #pragma unroll
                     for (int j = 0; j < BPL; j++) dma16p<CPL>(dst + uint32_t(j) * 1024u, base, L.off[b][j]);
+                } else if (LPRED && ((t.vend - t.b0) & 15u) == 0) {
+                    // piece 0 of every row lies inside the tile: no instruction is fully masked
+                    const uint8_t *base = uniform_ptr(a.data[node] + (uint64_t(g) * sc + t.b0));
+#pragma unroll
+                    for (int j = 0; j < BPL; j++) {
+                        const uint64_t mask = __builtin_amdgcn_ballot_w64(k16_of(L, j, b) + 16u <= t.vend - t.b0);
+                        dma16_masked(dst + uint32_t(j) * 1024u, base, L.off[b][j], mask);
+                    }
                 } else {
                     // partial tile: a piece straddling vend is read from vend - 16 (patched
                     // after landing), a piece wholly past vend from b0 (never used)
@@ -508,8 +535,21 @@ struct StreamEnc {
             pair_halves(cv, lo, hi);
             uint32_t off = (z - (odd ? PAIR : 0u)) * uint32_t(a.sc);
             asm volatile("" : "+v"(off));  // keep the 16 (node, layer) offsets out of LICM
-            off += t.b0 + prel + (odd ? 128u : 0u);
+            // the lane's position in the tile, from an opaque copy of the lane id (two VALU
+            // instructions per store pair rather than a register held across the tile loop)
+            uint32_t pos = prel + (odd ? 128u : 0u);
+            if constexpr (!PSWAP) {
+                uint32_t l = threadIdx.x;
+                asm volatile("" : "+v"(l));
+                pos = (l & 15u) << 4;  // part = lane bits 0-2, odd = bit 3
+            }
+            off += t.b0 + pos;
             const uint8_t *base = uniform_ptr(a.par[X]);  // SGPR base (also under the probes' deferred flow)
+            // A tile narrower than 256 (width a multiple of 16): lanes whose piece lies past vend
+            // sit the two stores out.  Piece 0 of every row is inside every tile, so part 0 of the
+            // even columns is active in every wave: both instructions always issue (the counted
+            // waits of the LOADERS == 0 variant rely on it).
+            if (pos + 16u > t.vend - t.b0) return;
             if constexpr (CHECK) {
                 // probe bounds check (stream_probe "f"): flag and skip a store outside par[X]
                 const uint64_t lim = uint64_t(a.sc) * 256u;
@@ -614,7 +654,9 @@ struct StreamEnc {
 // XOR into a per-lane sink, stored once at the end under a run-time predicate the compiler cannot
 // fold -- the live-math "no stores" variants (262144: reads + math; 262146: math only);
 // 524288 = CHECK (probe): every parity store and timing record is bounds-checked, a violation is
-// flagged in a.par[5] (atomicOr of a bit per kind) and the access skipped.  Bit 4
+// flagged in a.par[5] (atomicOr of a bit per kind) and the access skipped;
+// 2097152 = the previous tile map (StreamMap) with its whole-tile plain-store path, 4194304 = LPRED
+// (StreamEnc): narrow tiles load with masked lanes instead of clamped addresses.  Bit 4
 // (no end-of-group work at all) lets the compiler delete the math and is kept only as a record
 // of that (PROBE 4 / 6 compiled to 4 / 3 v_bitop3).
 // Segment timing of the probe instantiations (PROBE bit 4096): s_memtime cycles summed per
@@ -661,17 +703,26 @@ constexpr int kStreamEncMap = 8;
 template <int KD, int LOADERS, int PROBE = 0, int MAP = 0>
 __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_encode(BsArgs a) {
     using Kn = StreamEnc<KD, LOADERS, (PROBE >> 6) & 3, (PROBE >> 8) & 3, ((PROBE >> 10) & 1) == 0, (PROBE & 262144) != 0,
-                         (PROBE & 524288) != 0, MAP>;
+                         (PROBE & 524288) != 0, MAP, (PROBE & 4194304) != 0>;
     uint32_t sink = 0;  // SINK probes only
     constexpr bool TM = (PROBE & 4096) != 0;
     using K6 = typename Kn::K6;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, ns = a.nslots;
+    // PROBE 2097152 (probe builds): the previous tile map (StreamMap: full rounds + one narrow last
+    // tile, which takes the plain-store path whole) for the same-box A/B against BalancedMap
+    constexpr bool OLDMAP = (PROBE & (2048 | 2097152)) != 0;
     const auto tm = [&] {
         if constexpr ((PROBE & 2048) != 0) return ChipMap(uint32_t(a.sc), blockIdx.x, gridDim.x);
-        else return StreamMap(uint32_t(a.sc), a.tiles_per_xcd, ns, xcd, slot);
+        else if constexpr (OLDMAP) return StreamMap(uint32_t(a.sc), a.tiles_per_xcd, ns, xcd, slot);
+        else return BalancedMap(uint32_t(a.sc), a.tiles_per_xcd, ns, xcd, slot);
     }();
+    // the plain-store path: only the tile whose end is not a multiple of 16 (sc % 16 == 8: the one
+    // holding the end of the row); every other tile stores in DPP pairs, predicated on its width
+    const auto is_ragged = [](StreamTile t) BS_INL {
+        return OLDMAP ? t.vend < t.b0 + uint32_t(Kn::W) : ((t.vend - t.b0) & 15u) != 0;
+    };
     const int ntile = tm.ntile();
     if (ntile == 0) return;  // uniform per workgroup
     const int nsteps = ntile * Kn::STEPS;
@@ -758,7 +809,7 @@ __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_enco
     int pend = -1;
     StreamTile pt{0, 0};
     auto end_any = [&](int ge, StreamTile t) BS_INL {
-        const bool ragged = t.vend < t.b0 + uint32_t(Kn::W);
+        const bool ragged = is_ragged(t);
         // opaque per-call copy of the column: the store rows derived from it are computed here,
         // not hoisted out of the tile loop into long-lived (spilled) registers
         int cc = c;
@@ -845,7 +896,7 @@ __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_enco
         if constexpr (TM) T.add(1, y, t0);
         if (y == 2 && !(PROBE & 4)) {
             const StreamTile t = tm.tile(k, slot, ns);
-            const bool ragged = t.vend < t.b0 + uint32_t(Kn::W);
+            const bool ragged = is_ragged(t);
             const int ge = (PROBE & 32) ? ((g + int(slot)) & 3) : g;
             if constexpr (DEFER) {
                 pend = ge;
