@@ -116,8 +116,10 @@ def set_exec_mode(mode: str) -> str:
     """Process-wide plan executor for decode / repair / staged encode (clay.h): 'auto' (tile-fused
     where the U slots fit in LDS, else grouped; for q = 4, t = 4 codes the local decode for
     erasures in one y-section plus at most one other, the fused decode v2 for 3-4 erasures in
-    distinct y-sections; the bit-sliced repair kernels for q = m repairs from all n - 1 nodes),
-    'grouped' (one launch per level), 'tile', 'stream' (every decode a streaming kernel takes:
+    distinct y-sections; the bit-sliced repair kernels for q = m repairs from all n - 1 nodes,
+    batched repairs of those in one launch, last path 'bs-repair-batch'),
+    'grouped' (one launch per level; batched decodes and repairs 'grouped-batch'), 'tile',
+    'stream' (every decode a streaming kernel takes:
     local, else fused v2 from 2 erasures; the streaming repair kernel at any sub-chunk size),
     'stream-local' or 'stream-fused2' (that kernel wherever it applies).  Modes choose kernels
     only: every mode returns the reference's bytes on any input.  Returns the previous mode."""
@@ -130,7 +132,8 @@ def set_exec_mode(mode: str) -> str:
 def last_exec_path() -> str:
     """Plan executor of this thread's last decode / repair / staged encode: 'tile' | 'grouped' |
     'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
-    'bs-decode1-batch' | 'grouped-batch' (the batched decodes) | 'none'."""
+    'bs-decode1-batch' (the batched decodes) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
+    (both) | 'none'."""
     return _lib.lib().clay_last_exec_path().decode()
 
 
@@ -423,5 +426,44 @@ class ClayCode:
         rc = _lib.lib().clay_repair_device(C.byref(self._c), int(lost_node), _sizes(ids), hp,
                                            len(ids), int(chunk_size), C.c_void_p(_ptr(out)),
                                            int(device), C.c_void_p(int(stream)), C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def repair_device_strided(self, lost_node: int, helper_ids: Sequence[int], helpers, out, n_stripes: int,
+                              chunk_size: int, full_chunks: bool = False, node_stride: int = 0,
+                              stripe_stride: int = 0, out_stripe_stride: int = 0, device: int = 0,
+                              stream: int = 0):
+        """Batched repair of stripes with the same lost node and helper set at fixed strides (clay.h
+        clay_repair_device_strided): the helper buffer of node id of stripe s is at
+        helpers + s * stripe_stride + id * node_stride (indexed by node id), the rebuilt chunk goes
+        to out + s * out_stripe_stride.  full_chunks: helper buffers are whole chunks, else the
+        beta repair sub-chunks in minimum_to_repair order.  Strides default to a contiguous
+        [n_stripes][n][chunk_size or beta * sub-chunk] input and a [n_stripes][chunk_size] output."""
+        hb = int(chunk_size) if full_chunks else self.beta * (int(chunk_size) // self.sub_chunk_no)
+        ns_ = node_stride or hb
+        ss_ = stripe_stride or self.n * ns_
+        oss = out_stripe_stride or int(chunk_size)
+        ids = list(helper_ids)
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_repair_device_strided(C.byref(self._c), int(lost_node), _sizes(ids), len(ids),
+                                                   C.c_void_p(_ptr(helpers)), ns_, ss_, 1 if full_chunks else 0,
+                                                   C.c_void_p(_ptr(out)), oss, int(n_stripes), int(chunk_size),
+                                                   int(device), C.c_void_p(int(stream)), C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def repair_device_batch(self, lost_node: int, helper_ids: Sequence[int], helper_bufs, outs, n_stripes: int,
+                            chunk_size: int, full_chunks: bool = False, device: int = 0, stream: int = 0):
+        """Batched repair, pointer-array form (clay.h clay_repair_device_batch): helper_bufs holds
+        n_stripes * len(helper_ids) entries, stripe s's buffer of helper_ids[h] at
+        [s * len(helper_ids) + h]; outs holds one output per stripe."""
+        ids = list(helper_ids)
+        hp = (C.c_void_p * max(1, len(ids) * int(n_stripes)))(*[(_ptr(x) if x is not None else None)
+                                                                for x in helper_bufs])
+        op = (C.c_void_p * max(1, int(n_stripes)))(*[(_ptr(x) if x is not None else None) for x in outs])
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_repair_device_batch(C.byref(self._c), int(lost_node), _sizes(ids), hp, len(ids),
+                                                 1 if full_chunks else 0, op, int(n_stripes), int(chunk_size),
+                                                 int(device), C.c_void_p(int(stream)), C.byref(err))
         if rc:
             _raise(rc, err)

@@ -58,6 +58,10 @@ SIGNATURES = {
                                      _err_p]),
     "clay_repair_device_full_chunks": (C.c_int, [_code_p, _sz, _P(_sz), _P(_vp), _sz, _sz, _vp,
                                                  C.c_int, _vp, _err_p]),
+    "clay_repair_device_strided": (C.c_int, [_code_p, _sz, _P(_sz), _sz, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                             C.c_void_p, C.c_int64, _sz, _sz, C.c_int, C.c_void_p, _err_p]),
+    "clay_repair_device_batch": (C.c_int, [_code_p, _sz, _P(_sz), _P(_vp), _sz, C.c_int, _P(_vp), _sz, _sz, C.c_int,
+                                           _vp, _err_p]),
     "clay_reserve_workspace": (C.c_int, [_code_p, _sz, C.c_int, _err_p]),
     "clay_release_workspace": (C.c_int, [C.c_int, _err_p]),
     "clay_release_captured": (C.c_int, [C.c_int, _err_p]),

@@ -285,6 +285,7 @@ static Tuning read_tuning() {
     const long long ring = ival("CLAY_DECODE_RING", 10);
     t.decode_ring = uint32_t(ring >= 6 && ring <= 10 ? ring : 10);
     t.local_w64 = ival("CLAY_LOCAL_W64", 0) != 0;
+    t.repair_batch_jfast = int(ival("CLAY_REPAIR_BATCH_JFAST", -1));
     return t;
 }
 // namespace-scope: initialised when the library is loaded, before any ABI call

@@ -33,6 +33,7 @@
 #include "bitslice.hpp"
 #include "stream_encode.hpp"
 #include "repair_args.hpp"  // bit-sliced repair kernel: repair_kernel.hpp, instantiated in repair_stream.hip
+#include "repair_batch_map.hpp"  // its batch form's column map
 #include "decode_args.hpp"  // streaming-decode kernel: stream_decode.hpp, instantiated in decode_stream.hip
 #include "line_args.hpp"  // line-local bit-sliced (4,2,5) encode / single-erasure decode: bitslice_line.hpp, in line_kernels.hip
 #include "kernels.hpp"
@@ -2664,6 +2665,153 @@ static Error repair_device_impl(const clay_code_t *code, size_t lost, const size
     return run_plan(cs, *plan, dev, *ds, static_cast<hipStream_t>(stream), P, chunk / c.sub_chunk_no, chunk);
 }
 
+// ---- batched repair: n_stripes stripes with the same lost node and helper set
+// (clay_repair_device_strided / clay_repair_device_batch) ----
+// repair_stream.hip: the batch form of k_bs_repair; 1 launched, 0 no instantiation, < 0 HIP error
+int launch_bs_repair_batch_kernel(int k, int m, int y0, const bs::RepArgs &a, hipStream_t stream, bool jfast);
+
+// Lane order of the batch k_bs_repair.  With the part the fastest lane index (the single-stripe
+// kernel's order) and one or two columns per stripe, consecutive lanes read 32 bytes each from
+// different stripes; with the plane layer j fastest a wave reads the adjacent rows of one stripe.
+// Measured (profiles/r08/lane_order.txt): j-fastest wins at sc = 16, 32 and 48
+// for all three codes (3-36 %), ties or loses at 64 and loses at 128 and 320 (5-30 %), so it
+// runs while a stripe has under two whole columns (49..63 are not measured).
+constexpr size_t kRepairBatchJfastMaxSc = 63;
+
+// Stripes at fixed strides: the helper buffer of external node i of stripe s at helpers +
+// s * stripe + i * node, the rebuilt chunk at out + s * ostripe.
+struct RepStrided {
+    const uint8_t *helpers;
+    int64_t node, stripe;
+    uint8_t *out;
+    int64_t ostripe;
+};
+
+// bufs: n_stripes x nh helper pointers and outs: n_stripes outputs (sd == nullptr), or the strided
+// layout `sd`.  `full`: helper buffers are whole chunks (clay_repair_device_full_chunks), else the
+// beta repair sub-chunks (clay_repair_device).
+static Error repair_batch_impl(const clay_code_t *code, size_t lost, const size_t *ids, const uint8_t *const *bufs,
+                               size_t nh, bool full, uint8_t *const *outs, size_t n_stripes, size_t chunk, int dev,
+                               void *stream, const RepStrided *sd) {
+    Error e = check_code(code);
+    if (e) return e;
+    const clay_code_t &c = *code;
+    std::vector<uint8_t> hin;
+    std::vector<long> slot_of;
+    std::vector<size_t> sub;
+    e = validate_repair(c, lost, ids, nullptr, nh, chunk, hin, slot_of, sub);
+    if (e) return e;
+    if (sd ? !sd->helpers : !bufs)
+        return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null helper buffer");
+    if (sd ? !sd->out : !outs) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
+    auto hptr = [&](size_t s, size_t h) -> const uint8_t * {
+        return sd ? sd->helpers + int64_t(s) * sd->stripe + int64_t(ids[h]) * sd->node : bufs[s * nh + h];
+    };
+    auto optr = [&](size_t s) -> uint8_t * { return sd ? sd->out + int64_t(s) * sd->ostripe : outs[s]; };
+    if (!sd)
+        for (size_t s = 0; s < n_stripes; s++) {
+            for (size_t h = 0; h < nh; h++)
+                if (!bufs[s * nh + h])
+                    return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null helper buffer");
+            if (!outs[s]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
+        }
+    if (n_stripes == 0) return Error{};
+    t_last_launches = 0;
+    DevState *ds;
+    e = dev_state(dev, &ds);
+    if (e) return e;
+    DeviceGuard g(dev);
+    const size_t tn = c.q * c.t;
+    if (tn > size_t(kMaxTn))
+        return make_error(CLAY_ERR_DEVICE, tn, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
+    CodeState &cs = *code_state(c);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int xm = g_exec_mode.load(std::memory_order_relaxed);
+    // The thresholds are the encode's (kBatchMinStripes, kBatchMaxStripeBytes: DESIGN.md §4.4), as
+    // for the batched decode; nobody has measured them for repair.
+    const bool small = c.k * chunk <= kBatchMaxStripeBytes;
+    const size_t sc = chunk / c.sub_chunk_no;
+    // repair batch: the column-flattened k_bs_repair (repair_kernel.hpp), ONE launch for any number
+    // of stripes: q = m codes with every other node a helper, auto / "stream", the stripes at
+    // uniform strides (the strided form, or pointer arrays that are rows of one buffer).  Any
+    // sub-chunk size and alignment, both layouts; no allocation, no pointer table: capturable
+    // unprepared.
+    if ((xm == kExecAuto || xm == kExecStream) && small && c.q == c.m && tn <= 16 && nh + 1 == c.n) {
+        bs::RepArgs ra{};
+        const size_t lost_int = internal_of(c, lost);
+        bool ok = true;
+        for (size_t in = 0; in < tn; in++) {
+            if (in == lost_int || (in >= c.k && in < c.k + c.nu)) continue;
+            if (slot_of[in] < 0) ok = false;
+            else ra.h[in] = hptr(0, size_t(slot_of[in]));
+        }
+        const int64_t sin = sd ? sd->stripe : n_stripes > 1 ? int64_t(hptr(1, 0) - hptr(0, 0)) : 0;
+        const int64_t sout = sd ? sd->ostripe : n_stripes > 1 ? int64_t(optr(1) - optr(0)) : 0;
+        if (ok && !sd)
+            for (size_t s = 1; s < n_stripes && ok; s++) {
+                for (size_t h = 0; h < nh && ok; h++) ok = hptr(s, h) == hptr(0, h) + int64_t(s) * sin;
+                ok = ok && optr(s) == optr(0) + int64_t(s) * sout;
+            }
+        const uint64_t cps = bs::rep_batch_cps(sc);
+        if (cps >= 0xFFFFFFFFull || n_stripes >= 0xFFFFFFFFull || cps * n_stripes >= 0xFFFFFFFFull) ok = false;  // 32-bit columns
+        if (ok) {
+            ra.out = optr(0);
+            ra.sc = sc;
+            ra.x0 = uint32_t(lost_int % c.q);
+            ra.full = full ? 1u : 0u;
+            ra.cps = uint32_t(cps);
+            ra.ncols = uint32_t(cps * n_stripes);
+            ra.sin = sin;
+            ra.sout = sout;
+            const int jt = tuning().repair_batch_jfast;
+            const bool jfast = jt < 0 ? sc <= kRepairBatchJfastMaxSc : jt != 0;
+            const int r = launch_bs_repair_batch_kernel(int(c.k), int(c.m), int(lost_int / c.q), ra, st, jfast);
+            if (r < 0) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "HIP error: %s", hipGetErrorString(hipError_t(-r)));
+            if (r > 0) {
+                t_last_launches += 1;
+                t_last_exec = "bs-repair-batch";
+                return Error{};
+            }
+        }
+    }
+    if (n_stripes >= kBatchMinStripes && small) {
+        // staged batch: the cached repair plan, one k_gexec launch per level for the whole batch
+        std::vector<uint8_t> key(hin);
+        key.push_back(uint8_t(lost & 0xFF));
+        key.push_back(uint8_t(lost >> 8));
+        key.push_back(uint8_t(full));
+        const Plan *plan = nullptr;
+        e = cached_plan(cs, cs.rep, key,
+                        [&](std::unique_ptr<Plan> &p) { return plan_repair(c, cs.rs, lost, hin, slot_of, sub, p, full); },
+                        &plan);
+        if (e) return e;
+        std::vector<size_t> bases;
+        for (size_t in = 0; in < tn; in++)
+            if (slot_of[in] >= 0) bases.push_back(tn + in);
+        bases.push_back(2 * tn + 1);
+        auto ptr_of = [&](size_t b, size_t s) -> uint8_t * {
+            return b == 2 * tn + 1 ? optr(s) : const_cast<uint8_t *>(hptr(s, size_t(slot_of[b - tn])));
+        };
+        size_t launches = 0;
+        e = run_plan_batch(cs, *ds, dev, *plan, bases, ptr_of, sd != nullptr, n_stripes, chunk, st, &launches);
+        if (e) return e;
+        t_last_launches += launches;
+        t_last_exec = "grouped-batch";
+        return Error{};
+    }
+    // few or large stripes: stripe by stripe
+    std::vector<const uint8_t *> hv(nh);
+    size_t launches = 0;
+    for (size_t s = 0; s < n_stripes; s++) {
+        for (size_t h = 0; h < nh; h++) hv[h] = hptr(s, h);
+        e = repair_device_impl(code, lost, ids, hv.data(), nullptr, nh, chunk, optr(s), dev, stream, full);
+        if (e) return e;
+        launches += t_last_launches;
+    }
+    t_last_launches = launches;
+    return Error{};
+}
+
 // ---------------------------------------------------------------------------
 // Host-side copies the API's semantics require (the returned data chunks, encode.rs:44-55 /
 // decode.rs:155-158), split over a few threads and run beside the GPU pipeline.
@@ -3000,6 +3148,24 @@ int clay_repair_device_full_chunks(const clay_code_t *code, size_t lost, const s
                                    void *stream, clay_error_t *err) {
     if (err) std::memset(err, 0, sizeof(*err));
     Error e = repair_device_impl(code, lost, ids, chunks, nullptr, nh, chunk, out, device, stream, true);
+    return e ? report(e, err) : 0;
+}
+
+int clay_repair_device_strided(const clay_code_t *code, size_t lost, const size_t *ids, size_t nh, const uint8_t *helpers,
+                               int64_t node_stride, int64_t stripe_stride, int full_chunks, uint8_t *out,
+                               int64_t out_stripe_stride, size_t ns, size_t chunk, int device, void *stream,
+                               clay_error_t *err) {
+    if (err) std::memset(err, 0, sizeof(*err));
+    const RepStrided sd{helpers, node_stride, stripe_stride, out, out_stripe_stride};
+    Error e = repair_batch_impl(code, lost, ids, nullptr, nh, full_chunks != 0, nullptr, ns, chunk, device, stream, &sd);
+    return e ? report(e, err) : 0;
+}
+
+int clay_repair_device_batch(const clay_code_t *code, size_t lost, const size_t *ids, const uint8_t *const *bufs, size_t nh,
+                             int full_chunks, uint8_t *const *outs, size_t ns, size_t chunk, int device, void *stream,
+                             clay_error_t *err) {
+    if (err) std::memset(err, 0, sizeof(*err));
+    Error e = repair_batch_impl(code, lost, ids, bufs, nh, full_chunks != 0, outs, ns, chunk, device, stream, nullptr);
     return e ? report(e, err) : 0;
 }
 

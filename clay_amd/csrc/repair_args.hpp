@@ -16,6 +16,10 @@ struct RepArgs {
                            // 0: the beta plane layers in ascending order (layer j at j * sc)
     uint32_t ntiles, per_xcd;
     uint64_t b_start;      // first byte position (k_bs_repair: tiles of [b_start, sc))
+    // batch form of k_bs_repair only (repair_batch_map.hpp): h[] / out are stripe 0's, stripe s
+    // reads at + s * sin and writes at + s * sout; tiles are runs of columns, not of positions
+    uint32_t ncols, cps;   // columns (32 positions of one stripe) in all / per stripe
+    int64_t sin, sout;
 };
 
 }  // namespace bs

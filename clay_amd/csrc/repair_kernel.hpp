@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "stream_encode.hpp"  // uniform_ptr
 #include "repair_args.hpp"
+#include "repair_batch_map.hpp"
 
 namespace clay {
 namespace bs {
@@ -144,11 +145,23 @@ struct BsRepair {
         }
     }
 
-    template <bool FULL>
+    // BATCH: b0 = the tile's first column (repair_batch_map.hpp); the lane's column gives its
+    // stripe, its position in the sub-chunk and the stripe's helper / output offsets
+    template <bool FULL, bool BATCH = false>
     __device__ static void tile(const RepArgs &a, uint32_t j, uint32_t part, uint64_t b0) {
         const uint64_t sc = a.sc;
-        const uint64_t pos = b0 + 32u * part;
-        const int nv = FULL ? 32 : int(pos >= sc ? 0 : (sc - pos > 32 ? 32 : sc - pos));
+        uint64_t pos, op;  // helper rows at + pos, output rows at + op (the stripe's offsets included)
+        int nv;
+        if constexpr (BATCH) {
+            const RepBatchCol c = rep_batch_col(uint32_t(b0) + part, a.ncols, a.cps, sc);
+            nv = FULL ? 32 : int(c.nv);
+            pos = uint64_t(int64_t(c.stripe) * a.sin) + c.pos;
+            op = uint64_t(int64_t(c.stripe) * a.sout) + c.pos;
+        } else {
+            pos = b0 + 32u * part;
+            op = pos;
+            nv = FULL ? 32 : int(pos >= sc ? 0 : (sc - pos > 32 ? 32 : sc - pos));
+        }
         if (!FULL && nv == 0) return;
         const uint32_t x0 = a.x0;
         auto row = [&](int i, uint32_t jj) BS_INL {  // helper of node i at plane layer jj
@@ -177,17 +190,18 @@ struct BsRepair {
                     constexpr int I = Y * Q + X;
                     uint32_t o[8], cv[8];
                     const bool keep = creal && zy != uint32_t(X);
-                    const uint8_t *op = real(I) ? row(I, j) : nullptr;
+                    const uint8_t *own = real(I) ? row(I, j) : nullptr;
                     const uint32_t jc = j + (uint32_t(X) - zy) * jw(Y);
                     const uint64_t l = a.full ? uint64_t(layer_of(jc, x0)) : uint64_t(jc);
                     if constexpr (FULL) {
                         // a masked companion is read from a valid row (its own) and discarded:
                         // no branch around the load, so loads of consecutive nodes overlap
-                        const uint8_t *cq = keep ? cp + l * sc + pos : (real(I) ? op : a.out + pos);
-                        if constexpr (real(I)) ld32v(o, op);
+                        // (batch: the dummy read stays inside the stripe's own output rows)
+                        const uint8_t *cq = keep ? cp + l * sc + pos : (real(I) ? own : a.out + op);
+                        if constexpr (real(I)) ld32v(o, own);
                         ld32v(cv, cq);
                     } else {
-                        if constexpr (real(I)) ld32<false, true>(o, op, nv);
+                        if constexpr (real(I)) ld32<false, true>(o, own, nv);
                         if (keep) {
                             ld32<false, true>(cv, cp + l * sc + pos, nv);
                         } else {
@@ -218,7 +232,7 @@ struct BsRepair {
             for (int w = 0; w < 8; w++) v[w] = acc[X * 8 + w];
             transpose8(v);
             if (uint32_t(X) == x0) {
-                st32o<FULL>(a.out + uint64_t(zj) * sc + pos, v, nv);
+                st32o<FULL>(a.out + uint64_t(zj) * sc + op, v, nv);
             } else {
                 if constexpr (real(I)) {
                     uint32_t c[8];
@@ -231,7 +245,7 @@ struct BsRepair {
 #pragma unroll
                 for (int w = 0; w < 8; w++) v[w] = gf_mul(v[w], tg);
                 const uint32_t zo = zj + (uint32_t(X) - x0) * wt(Y0);
-                st32o<FULL>(a.out + uint64_t(zo) * sc + pos, v, nv);
+                st32o<FULL>(a.out + uint64_t(zo) * sc + op, v, nv);
             }
         });
     }
@@ -569,16 +583,33 @@ __global__ __launch_bounds__((BsRepairStream<KD, M, Y0, PARTS, LOADERS>::BLOCK))
 }
 
 // grid = 8 * per_xcd blocks: XCD x streams tiles [x * per_xcd, (x + 1) * per_xcd)
-template <int KD, int M, int Y0>
+// BATCH: many stripes with the same lost node and helper set in one launch (RepArgs ncols, cps,
+// sin, sout).  Tiles are flattened over COLUMNS (32 positions of one stripe, repair_batch_map.hpp),
+// not over one stripe's positions: tile t owns columns [t * PARTS, +PARTS), so small sub-chunks
+// fill the workgroup with several stripes and tiles may straddle stripe boundaries.  A workgroup
+// still holds every plane layer of each of its columns (the PRT companions are read by its other
+// lanes).  The unmasked variant runs where every lane has a whole column.
+// JF (batch form only): the plane layer j is the fastest lane index instead of the part, so
+// consecutive lanes read consecutive rows of one column (adjacent in the gathered layout when
+// sc = 32) instead of the same row of consecutive columns.
+template <int KD, int M, int Y0, bool BATCH = false, bool JF = false>
 __global__ __launch_bounds__(256) void k_bs_repair(RepArgs a) {
     using Kn = BsRepair<KD, M, Y0>;
+    static_assert(BATCH || !JF, "lane order: a choice of the batch form");
     if (threadIdx.x >= uint32_t(Kn::LANES)) return;
     const uint32_t tix = (blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
     if (tix >= a.ntiles) return;
-    const uint32_t j = threadIdx.x / uint32_t(Kn::PARTS), part = threadIdx.x % uint32_t(Kn::PARTS);
-    const uint64_t b0 = a.b_start + uint64_t(tix) * Kn::W;
-    if (b0 + Kn::W <= a.sc) Kn::template tile<true>(a, j, part, b0);
-    else Kn::template tile<false>(a, j, part, b0);
+    const uint32_t j = JF ? threadIdx.x % uint32_t(Kn::P) : threadIdx.x / uint32_t(Kn::PARTS);
+    const uint32_t part = JF ? threadIdx.x / uint32_t(Kn::P) : threadIdx.x % uint32_t(Kn::PARTS);
+    if constexpr (BATCH) {
+        const uint64_t c0 = uint64_t(tix) * Kn::PARTS;
+        if (rep_batch_tile_full(tix, uint32_t(Kn::PARTS), a.ncols, a.sc)) Kn::template tile<true, true>(a, j, part, c0);
+        else Kn::template tile<false, true>(a, j, part, c0);
+    } else {
+        const uint64_t b0 = a.b_start + uint64_t(tix) * Kn::W;
+        if (b0 + Kn::W <= a.sc) Kn::template tile<true>(a, j, part, b0);
+        else Kn::template tile<false>(a, j, part, b0);
+    }
 }
 
 }  // namespace bs

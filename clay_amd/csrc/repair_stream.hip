@@ -19,6 +19,30 @@ static hipError_t launch_one(bs::RepArgs a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// batch form: a.h / a.out are stripe 0's, a.sin / a.sout / a.cps / a.ncols set by the caller
+// (ncols fits 32 bits); tiles of PARTS columns in the XCD-contiguous order of launch_one
+template <int KD, int M, int Y0, bool JF>
+static hipError_t launch_one_batch(bs::RepArgs a, hipStream_t stream) {
+    using Kn = bs::BsRepair<KD, M, Y0>;
+    a.b_start = 0;
+    a.ntiles = uint32_t(bs::rep_batch_ntiles(a.ncols, uint32_t(Kn::PARTS)));
+    a.per_xcd = (a.ntiles + 7) / 8;
+    bs::k_bs_repair<KD, M, Y0, true, JF><<<dim3(a.per_xcd * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+template <int KD, int M, bool JF>
+static hipError_t launch_km_batch(int y0, const bs::RepArgs &a, hipStream_t stream) {
+    switch (y0) {
+    case 0: return launch_one_batch<KD, M, 0, JF>(a, stream);
+    case 1: return launch_one_batch<KD, M, 1, JF>(a, stream);
+    case 2: return launch_one_batch<KD, M, 2, JF>(a, stream);
+    default:
+        if constexpr (bs::Shape<KD, M>::T > 3) return launch_one_batch<KD, M, 3, JF>(a, stream);
+        return hipErrorInvalidValue;
+    }
+}
+
 // streaming variant: one workgroup per CU; returns hipErrorNotSupported when the launch should
 // fall back to the direct kernel
 template <int KD, int M, int Y0, int PARTS, int LOADERS>
@@ -105,6 +129,20 @@ int launch_bs_repair_kernel(int k, int m, int y0, const bs::RepArgs &a, hipStrea
     if (e == hipErrorNotSupported && stream_mode == 3) return 0;
     if (e != hipSuccess) return -int(e);
     return streamed ? 2 : 1;
+}
+
+// Batch form of k_bs_repair (column-flattened, repair_batch_map.hpp): one launch for every stripe
+// of the batch.  Returns 1 = launched, 0 = no instantiation for (k, m), < 0 = HIP error.
+// jfast: the j-fastest lane order (the caller's rule: engine.hip kRepairBatchJfastMaxSc).
+int launch_bs_repair_batch_kernel(int k, int m, int y0, const bs::RepArgs &a, hipStream_t stream, bool jfast) {
+    hipError_t e;
+    if (a.ncols == 0 || a.cps == 0) return 0;
+    if (k == 9 && m == 3) e = jfast ? launch_km_batch<9, 3, true>(y0, a, stream) : launch_km_batch<9, 3, false>(y0, a, stream);
+    else if (k == 10 && m == 4) e = jfast ? launch_km_batch<10, 4, true>(y0, a, stream) : launch_km_batch<10, 4, false>(y0, a, stream);
+    else if (k == 4 && m == 2) e = jfast ? launch_km_batch<4, 2, true>(y0, a, stream) : launch_km_batch<4, 2, false>(y0, a, stream);
+    else return 0;
+    if (e != hipSuccess) return -int(e);
+    return 1;
 }
 
 }  // namespace clay

@@ -38,6 +38,9 @@ struct Tuning {
     uint32_t decode_ring = 10;   // CLAY_DECODE_RING
     // local decode: the 64-byte-tile kernel also for one erasure in section G (A/B measurements)
     bool local_w64 = false;      // CLAY_LOCAL_W64
+    // batched repair: lane order of the batch k_bs_repair (A/B measurements): 0 = part-fastest,
+    // 1 = j-fastest at every sub-chunk size; < 0: the built-in rule (engine.hip)
+    int repair_batch_jfast = -1;  // CLAY_REPAIR_BATCH_JFAST
 };
 
 // The knobs as read at load time.

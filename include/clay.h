@@ -260,6 +260,45 @@ int clay_repair_device_full_chunks(const clay_code_t *code, size_t lost_node, co
                                    size_t chunk_size, uint8_t *out, int device, void *stream,
                                    clay_error_t *err);
 
+/* Batched repair of n_stripes stripes with the SAME lost node and helper set, laid out at fixed
+ * strides in device memory (the reference repairs one stripe per call, repair.rs:140-421; after a
+ * node failure a store of small stripes rebuilds the same node in every one of them, at the
+ * launch-bound stripe sizes of benches/clay_bench.rs).  The helper buffer of external node
+ * id = helper_ids[h] of stripe s is at helpers + s*stripe_stride + id*node_stride: it is indexed by
+ * node id, not by h, so a [n_stripes][n][...] buffer is passed as it is; the slots of nodes not in
+ * helper_ids (the lost node's included) are never read.  full_chunks == 0: a helper buffer holds
+ * the beta repair sub-chunks concatenated in minimum_to_repair order (clay_repair_device's layout);
+ * full_chunks != 0: it is the whole chunk (clay_repair_device_full_chunks's layout).  The rebuilt
+ * chunk of stripe s goes to out + s*out_stripe_stride.  With full_chunks, out may be
+ * helpers + lost_node*node_stride with out_stripe_stride == stripe_stride (rebuild into the lost
+ * slot); otherwise output regions must not overlap any region that is read.  Validation runs once,
+ * before any device work, exactly as clay_repair_device's (repair.rs:140-211), plus a NULL check of
+ * the base pointers; n_stripes == 0 validates, returns CLAY_OK and launches nothing.  Each stripe's
+ * output bytes are those of clay_repair_device / clay_repair_device_full_chunks for that stripe
+ * alone, on any input (helpers need not come from a codeword).
+ * Paths (clay_set_exec_mode): stripes of <= 4 MiB of data each run as a batch -- q = m codes with
+ * a k_bs_repair instantiation ((4,2,5), (9,3,11), (10,4,13)) repaired from all n - 1 other nodes
+ * as ONE launch of the batched k_bs_repair for any number of stripes (last exec path
+ * "bs-repair-batch", any sub-chunk size and alignment, both layouts; allocates nothing, so it may
+ * be captured unprepared), anything else, from 4 stripes, as one k_gexec launch per level of the
+ * repair plan ("grouped-batch"; inside a stream capture it must have been prepared by one call of
+ * the same shape); fewer or larger stripes run stripe by stripe as clay_repair_device.
+ * Asynchronous on `stream`. */
+int clay_repair_device_strided(const clay_code_t *code, size_t lost_node, const size_t *helper_ids,
+                               size_t n_helpers, const uint8_t *helpers, int64_t node_stride,
+                               int64_t stripe_stride, int full_chunks, uint8_t *out,
+                               int64_t out_stripe_stride, size_t n_stripes, size_t chunk_size,
+                               int device, void *stream, clay_error_t *err);
+
+/* Pointer-array form of clay_repair_device_strided: stripe s uses helper_bufs[s*n_helpers + h] for
+ * helper_ids[h], and outs[s]; a NULL entry is CLAY_ERR_INVALID_PARAMETERS.  Pointer arrays that are
+ * rows of one buffer (uniform stripe strides) take the same paths as the strided form; others run
+ * the batch through a cached device pointer table ("grouped-batch"). */
+int clay_repair_device_batch(const clay_code_t *code, size_t lost_node, const size_t *helper_ids,
+                             const uint8_t *const *helper_bufs, size_t n_helpers, int full_chunks,
+                             uint8_t *const *outs, size_t n_stripes, size_t chunk_size, int device,
+                             void *stream, clay_error_t *err);
+
 /* ------------------------------------------------------------------ */
 /* Engine control / introspection                                      */
 /* ------------------------------------------------------------------ */
@@ -342,11 +381,16 @@ int clay_set_encode_path(int mode);
  *                data): (4,2,5) with one erasure at uniform stripe strides in one launch of
  *                the batched k_bs_decode1 ("bs-decode1-batch"), every other code, pattern or
  *                layout, from 4 stripes, one k_gexec launch per plan level for the whole batch
- *                ("grouped-batch")
+ *                ("grouped-batch"); batched repairs (clay_repair_device_strided / _batch, same
+ *                stripe sizes): q = m codes with a k_bs_repair instantiation from all n - 1 other
+ *                nodes at uniform stripe strides in one launch of the batched k_bs_repair
+ *                ("bs-repair-batch"), every other code, helper set or layout, from 4 stripes,
+ *                "grouped-batch"
  *   1 grouped -- always the grouped executor (k_gexec, one launch per level); batched decodes
- *                always "grouped-batch" (the A/B partner of the line batch)
+ *                and repairs always "grouped-batch" (the A/B partner of the line / repair batch)
  *   2 tile    -- the tile executor wherever its U slots fit, whatever the plan size; batched
- *                decodes as under grouped ("grouped-batch": the tile executor has no batch form)
+ *                decodes and repairs as under grouped ("grouped-batch": the tile executor has no
+ *                batch form)
  *   (auto and stream: repair of (9,3,11), (10,4,13), (4,2,5) from all n - 1 other nodes runs
  *    the bit-sliced repair kernels: k_bs_repair_stream (LDS-DMA streaming, one workgroup per
  *    CU; auto when the sub-chunk gives every CU a tile, stream for any sub-chunk >= 16 bytes
@@ -373,7 +417,8 @@ int clay_set_exec_mode(int mode);
  * (k_stream_local), "stream-fused2"
  * (k_stream_fused2), "bs-decode1" (k_bs_decode1), "bs-repair-stream" (k_bs_repair_stream),
  * "bs-repair" (k_bs_repair), the batched decodes' "bs-decode1-batch" (k_bs_decode1 over many
- * stripes) and "grouped-batch" (k_gexec over many stripes), or "none". */
+ * stripes), the batched repairs' "bs-repair-batch" (k_bs_repair over many stripes), both batches'
+ * "grouped-batch" (k_gexec over many stripes), or "none". */
 const char *clay_last_exec_path(void);
 
 /* Name of the path the last encode on this thread used ("fused-q4w128p8", "staged", ...). */

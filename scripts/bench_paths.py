@@ -195,6 +195,66 @@ def decode_batch_cfg(k, m, d, stripe, n, e, loop_stripes):
         clay_amd.set_exec_mode(prev)
 
 
+def repair_batch_cfg(k, m, d, sc, n, lost, loop_stripes, full):
+    """One lost node in every stripe, n stripes of sub-chunk size sc per call (about 64 MiB of
+    chunks): clay_repair_device_strided under auto (the repair batch where the code has a
+    k_bs_repair instantiation) and under "grouped" (the staged batch), samples alternated; then the
+    only way without a batch entry point, a loop of per-stripe clay_repair_device(_full_chunks)
+    calls on the same buffers (the first loop_stripes stripes, reported per stripe; host and launch
+    overhead included: that is what the caller pays).  full: whole helper chunks, else the
+    gathered beta repair sub-chunks.  Bytes: (n - 1) x beta x sc read + the chunk written."""
+    c = ClayCode(k, m, d)
+    chunk = c.sub_chunk_no * sc
+    helpers = [h for h, _ in c.minimum_to_repair(lost, [i for i in range(c.n) if i != lost])]
+    hb = chunk if full else c.beta * sc
+    bufs = rnd(n * c.n, hb, 7).view(n, c.n, hb)
+    outs = torch.empty((n, chunk), dtype=torch.uint8, device="cuda")
+    per = len(helpers) * c.beta * sc + chunk
+    lay = "full chunks" if full else "gathered"
+    name = f"repair ({k},{m},{d}) batch {n} x sc {sc} ({c.k * chunk >> 10} KiB stripes) node {lost} {lay}"
+    extra = {"bytes_counted": "per stripe (n-1) x beta x sc read + 1 chunk written",
+             "lane_order": {"0": "part-fastest", "1": "j-fastest"}.get(os.environ.get("CLAY_REPAIR_BATCH_JFAST", ""), "default")}
+
+    def call(mode):
+        def fn():
+            clay_amd.set_exec_mode(mode)
+            c.repair_device_strided(lost, helpers, bufs, outs, n, chunk, full, 0, 0, 0, 0, stream.cuda_stream)
+        return fn
+
+    prev = clay_amd.set_exec_mode("auto")
+    try:
+        modes = ("auto", "grouped")
+        res = timed_alternating([call(mo) for mo in modes])
+        for mo, (ms, mn) in zip(modes, res):
+            call(mo)()
+            torch.cuda.synchronize()
+            report(f"{name} {mo}", ms, mn, n * per, dict(extra, per_stripe_us=round(ms * 1e3 / n, 6)))
+        clay_amd.set_exec_mode("auto")
+        nl = min(n, loop_stripes)
+        ins = [[bufs[s, h] for h in helpers] for s in range(nl)]
+        fn1 = c.repair_device_full_chunks if full else c.repair_device
+
+        def loop():
+            for s in range(nl):
+                fn1(lost, helpers, ins[s], chunk, outs[s], 0, stream.cuda_stream)
+
+        ts = []
+        for i in range(6):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            loop()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if i >= 1:
+                ts.append(e0.elapsed_time(e1))
+        ms, mn = float(np.median(ts)), float(np.min(ts))
+        report(f"{name} per-stripe loop of {nl}", ms, mn, nl * per,
+               dict(extra, per_stripe_us=round(ms * 1e3 / nl, 4), per_stripe_us_min=round(mn * 1e3 / nl, 4),
+                    per_stripe_us_max=round(float(np.max(ts)) * 1e3 / nl, 4)))
+    finally:
+        clay_amd.set_exec_mode(prev)
+
+
 def repair_cfg(k, m, d, chunk, lost):
     c = ClayCode(k, m, d)
     sc = chunk // c.sub_chunk_no
@@ -240,6 +300,12 @@ if __name__ == "__main__":
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 10 << 10, 6553, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 100 << 10, 655, 0, 655)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 1 << 20, 64, 0, 64)),
+            # the same stripe sizes with node 0 lost and repaired from all others (sc = stripe / 32),
+            # and the other two codes with a repair kernel at sc = 32 / 320; both helper layouts
+            *[("batch_repair", (lambda a=a, f=f: repair_batch_cfg(*a, f))) for f in (False, True) for a in
+              ((4, 2, 5, 32, 65536, 0, 1024), (4, 2, 5, 320, 6553, 0, 1024), (4, 2, 5, 3200, 655, 0, 655),
+               (4, 2, 5, 32768, 64, 0, 64), (10, 4, 13, 32, 585, 0, 585), (10, 4, 13, 320, 58, 0, 58),
+               (9, 3, 11, 32, 2157, 0, 1024), (9, 3, 11, 320, 215, 0, 215))],
             ("decode", lambda: decode_cfg(4, 2, 5, 64 << 20, [0])),
             ("decode", lambda: decode_cfg(10, 4, 13, 1 << 30, [0, 4, 8, 12])),
             ("decode", lambda: decode_cfg(10, 4, 13, 1 << 30, [0, 4, 8, 12], "grouped")),
