@@ -635,10 +635,14 @@ static int contains(const size_t *a, size_t n, size_t v) {
 }
 
 /* decode.rs:31-161 decode.  The HashMap is passed as parallel arrays; "first
- * chunk" (decode.rs:54-56) and the scan orders are the array order. */
-int oc_decode(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs, const size_t *lens,
-              size_t n_avail, const size_t *er, size_t n_er, uint8_t *out, size_t out_cap,
-              size_t *out_len, oc_error_t *err) {
+ * chunk" (decode.rs:54-56) and the scan orders are the array order.
+ * all_chunks = 0: the k data chunks, as the reference returns them (decode.rs:150-160).
+ * all_chunks = 1: every chunk decode_layered leaves behind, k data then m parity in external
+ * node order -- the erased parity nodes hold the C values of decode.rs:213-253, which the
+ * reference computes and drops; present nodes come back as given. */
+static int decode_impl(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs, const size_t *lens,
+                       size_t n_avail, const size_t *er, size_t n_er, uint8_t *out, size_t out_cap,
+                       size_t *out_len, oc_error_t *err, int all_chunks) {
     clear_err(err);
     gf_init();
     if (out_len) *out_len = 0;
@@ -686,10 +690,12 @@ int oc_decode(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs,
     for (size_t i = 0; i < n_er; i++) es[er[i] < p->k ? er[i] : er[i] + p->nu] = 1;
     int rc = decode_layered(p, es, chunks, chunk, sc, err);
     if (!rc) {
-        size_t need = p->k * chunk;
+        size_t need = (all_chunks ? p->n : p->k) * chunk;
         if (out_cap < need) rc = set_err(err, OC_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: output buffer too small");
         else {
             for (size_t i = 0; i < p->k; i++) memcpy(out + i * chunk, chunks[i], chunk);
+            if (all_chunks)
+                for (size_t j = 0; j < p->m; j++) memcpy(out + (p->k + j) * chunk, chunks[p->k + p->nu + j], chunk);
             if (out_len) *out_len = need;
         }
     }
@@ -697,6 +703,18 @@ int oc_decode(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs,
     free(chunks);
     free(es);
     return rc;
+}
+
+int oc_decode(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs, const size_t *lens,
+              size_t n_avail, const size_t *er, size_t n_er, uint8_t *out, size_t out_cap,
+              size_t *out_len, oc_error_t *err) {
+    return decode_impl(p, ids, bufs, lens, n_avail, er, n_er, out, out_cap, out_len, err, 0);
+}
+
+int oc_decode_chunks(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs, const size_t *lens,
+                     size_t n_avail, const size_t *er, size_t n_er, uint8_t *out, size_t out_cap,
+                     size_t *out_len, oc_error_t *err) {
+    return decode_impl(p, ids, bufs, lens, n_avail, er, n_er, out, out_cap, out_len, err, 1);
 }
 
 /* ---------------- repair.rs ---------------- */

@@ -80,6 +80,13 @@ int oc_encode(const oc_code_t *p, const uint8_t *data, size_t len, uint8_t *out,
 int oc_decode(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs,
               const size_t *lens, size_t n_avail, const size_t *erasures, size_t n_erasures,
               uint8_t *out, size_t out_cap, size_t *out_len, oc_error_t *err);
+/* oc_decode with every chunk returned: out holds n * chunk bytes, the k data chunks then the m
+ * parity chunks in external node order (external parity j = internal node j + nu).  Erased
+ * parity nodes hold the C values decode_layered computes (decode.rs:213-253) and the reference
+ * drops; present nodes come back unchanged.  Same arguments, validation and errors as oc_decode. */
+int oc_decode_chunks(const oc_code_t *p, const size_t *ids, const uint8_t *const *bufs,
+                     const size_t *lens, size_t n_avail, const size_t *erasures, size_t n_erasures,
+                     uint8_t *out, size_t out_cap, size_t *out_len, oc_error_t *err);
 int oc_minimum_to_repair(const oc_code_t *p, size_t lost, const size_t *avail, size_t n_avail,
                          size_t *helpers_out, size_t *n_helpers, size_t *idx_out,
                          size_t *n_idx, oc_error_t *err);

@@ -121,6 +121,7 @@ def lib():
         L.oc_encode.argtypes = [P(OcCode), u8p, sz, u8p, P(OcError)]
         L.oc_decode.argtypes = [P(OcCode), P(sz), P(u8p), P(sz), sz, P(sz), sz, u8p, sz,
                                 P(sz), P(OcError)]
+        L.oc_decode_chunks.argtypes = L.oc_decode.argtypes
         L.oc_minimum_to_repair.argtypes = [P(OcCode), sz, P(sz), sz, P(sz), P(sz), P(sz),
                                            P(sz), P(OcError)]
         L.oc_repair.argtypes = [P(OcCode), sz, P(sz), P(u8p), P(sz), sz, sz, u8p, P(OcError)]
@@ -270,20 +271,31 @@ class OracleClay:
     def encode(self, data) -> list:
         return [bytes(r) for r in self.encode_array(data)]
 
-    def decode(self, available: dict, erasures) -> bytes:
+    def _decode(self, fn, rows: int, available: dict, erasures) -> np.ndarray:
         ids = list(available.keys())
         arrs = [_as_np(available[i]) for i in ids]
         ptrs = (C.POINTER(C.c_uint8) * max(1, len(arrs)))(*[_u8(a) for a in arrs])
         lens = _sizes([a.size for a in arrs])
         er = _sizes(list(erasures))
-        cap = self.k * (arrs[0].size if arrs else 0)
+        cap = rows * (arrs[0].size if arrs else 0)
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         olen = C.c_size_t()
         err = OcError()
-        if lib().oc_decode(C.byref(self._c), _sizes(ids), ptrs, lens, len(ids), er,
-                           len(list(erasures)), _u8(out), cap, C.byref(olen), C.byref(err)):
+        if fn(C.byref(self._c), _sizes(ids), ptrs, lens, len(ids), er,
+              len(list(erasures)), _u8(out), cap, C.byref(olen), C.byref(err)):
             raise OracleError(err)
-        return out[:olen.value].tobytes()
+        return out[:olen.value]
+
+    def decode(self, available: dict, erasures) -> bytes:
+        return self._decode(lib().oc_decode, self.k, available, erasures).tobytes()
+
+    def decode_chunks(self, available: dict, erasures) -> np.ndarray:
+        """decode() with every chunk returned: an (n, chunk_size) uint8 array, k data rows then
+        m parity.  Erased parity rows hold what decode_layered computes for them
+        (decode.rs:213-253; the reference returns the data only); present rows come back as
+        given.  On a codeword every row equals encode_array's."""
+        out = self._decode(lib().oc_decode_chunks, self.n, available, erasures)
+        return out.reshape(self.n, out.size // self.n)
 
     def minimum_to_repair(self, lost: int, available) -> list:
         av = list(available)
