@@ -21,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <string>
 #include <thread>
@@ -40,6 +41,7 @@
 #include "plan.hpp"
 #include "tuning.hpp"
 #include "encode3_args.hpp"
+#include "stripe_layout.hpp"  // host only: where the operands of a batch of stripes live
 
 namespace clay {
 
@@ -1078,6 +1080,75 @@ static Error encode_plan(CodeState &cs, const Plan **out) {
     *out = cs.enc.get();
     return Error{};
 }
+// the decode plan of an erasure pattern (`erased` / `want` per internal node)
+static Error decode_plan(CodeState &cs, const std::vector<uint8_t> &erased, const std::vector<uint8_t> &want,
+                         const Plan **out) {
+    std::vector<uint8_t> key(erased);
+    key.insert(key.end(), want.begin(), want.end());
+    return cached_plan(cs, cs.dec, key,
+                       [&](std::unique_ptr<Plan> &p) { return plan_decode(cs.code, cs.rs, erased, want, p); }, out);
+}
+// the repair plan of a lost node and helper set (validate_repair's hin / slot_of / sub)
+static Error repair_plan(CodeState &cs, size_t lost, const std::vector<uint8_t> &hin, const std::vector<long> &slot_of,
+                         const std::vector<size_t> &sub, bool full, const Plan **out) {
+    std::vector<uint8_t> key(hin);
+    key.push_back(uint8_t(lost & 0xFF));
+    key.push_back(uint8_t(lost >> 8));
+    key.push_back(uint8_t(full));
+    return cached_plan(cs, cs.rep, key,
+                       [&](std::unique_ptr<Plan> &p) { return plan_repair(cs.code, cs.rs, lost, hin, slot_of, sub, p, full); },
+                       out);
+}
+
+// Open device `dev` for work on `code`: the device's state, `dev` current while this lives, the
+// code's cached state.  Every device entry point opens after validation (and after the
+// "no stripes" return), so invalid arguments are reported without a GPU.
+struct Opened {
+    DevState *ds = nullptr;
+    CodeState *cs = nullptr;
+    std::optional<DeviceGuard> guard;
+    Error open(const clay_code_t &c, int dev) {
+        Error e = dev_state(dev, &ds);
+        if (e) return e;
+        guard.emplace(dev);
+        cs = code_state(c);
+        return Error{};
+    }
+    // ... for the plan executor's operand bases (decode, repair)
+    Error open_max_tn(const clay_code_t &c, int dev) {
+        Error e = open(c, dev);
+        if (e) return e;
+        if (c.q * c.t > size_t(kMaxTn))
+            return make_error(CLAY_ERR_DEVICE, c.q * c.t, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
+        return Error{};
+    }
+};
+
+// The compile-time generator of the bit-sliced kernels' Shape S (M parity rows) must equal the
+// run-time one (same construction).
+template <class S, int M>
+static Error rs_matches(const CodeState &cs) {
+    for (int p = 0; p < M; p++)
+        for (int i = 0; i < S::K; i++)
+            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
+                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    return Error{};
+}
+
+// Byte tails: is any of the n pointers, or a stripe stride, off 8-byte alignment?  (NULL is aligned.)
+template <class T>
+static bool misaligned8(T *const *p, size_t n, int64_t stride = 0) {
+    bool any = (stride & 7) != 0;
+    for (size_t i = 0; i < n; i++) any |= (reinterpret_cast<uintptr_t>(p[i]) & 7u) != 0;
+    return any;
+}
+
+// The line kernels' launch shape (bitslice_line.hpp): tiles per XCD, and up to 8 workgroups per CU
+template <class Args>
+static void line_slots(Args &a, uint64_t tiles, const DevProps &prop) {
+    a.tiles_per_xcd = uint32_t((tiles + 7) / 8);
+    a.nslots = std::min(a.tiles_per_xcd, uint32_t(std::max(1, prop.cus / 8) * 8));
+}
 
 template <int VW, int MAXD>
 static void launch_gexec1(int mode, dim3 grid, dim3 block, hipStream_t stream, const ExecPtrs &ptrs,
@@ -1350,11 +1421,7 @@ static Error launch_bs(CodeState &cs, const hipDeviceProp_t &prop, const uint8_t
     using S = typename Kn::S;
     const clay_code_t &c = cs.code;
     if (int(c.k) != KD || int(c.m) != M || int(c.d) != KD + M - 1) return Error{};
-    // the compile-time generator must equal the run-time one (same construction)
-    for (int p = 0; p < M; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    if (Error e = rs_matches<S, M>(cs)) return e;
     const int per_cu = std::max(1, int((160 * 1024) / (Kn::LDS_WORDS * 4)));
     for (size_t s = 0; s < n_stripes; s++) {
         bs::BsArgs a{};
@@ -1365,9 +1432,7 @@ static Error launch_bs(CodeState &cs, const hipDeviceProp_t &prop, const uint8_t
         a.tiles_per_xcd = (a.ntiles + 7) / 8;
         const uint32_t max_slots = uint32_t(std::max(1, prop.multiProcessorCount / 8) * per_cu);
         a.nslots = std::min(max_slots, a.tiles_per_xcd);
-        bool bt = sc % 8 != 0;  // byte tails: unaligned rows or chunks
-        for (int i = 0; i < KD; i++) bt |= (reinterpret_cast<uintptr_t>(a.data[i]) & 7u) != 0;
-        for (int x = 0; x < M; x++) bt |= (reinterpret_cast<uintptr_t>(a.par[x]) & 7u) != 0;
+        const bool bt = sc % 8 != 0 || misaligned8(a.data, KD) || misaligned8(a.par, M);  // byte tails
         if (bt) bs::k_bs_encode<KD, M, PG, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
         else bs::k_bs_encode<KD, M, PG><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
         CLAY_HIP(hipGetLastError());
@@ -1390,10 +1455,7 @@ static Error launch_stream(CodeState &cs, const DevProps &prop, const uint8_t *c
     if (int(c.k) != KD || c.m != 4 || c.d != c.k + 3) return Error{};
     // per-lane DMA offsets are 32-bit chunk offsets; a clamped 16-byte piece needs sc >= 16
     if (double(S::ALPHA) * double(sc) >= 4294967296.0 || sc < 16) return Error{};
-    for (int p = 0; p < 4; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    if (Error e = rs_matches<S, 4>(cs)) return e;
     Error ae = lds_attr_once(reinterpret_cast<const void *>(&bs::k_stream_encode<KD, LOADERS, 0, bs::kStreamEncMap>),
                              Kn::LDS_BYTES, prop.dev);
     if (ae) return ae;
@@ -1429,10 +1491,7 @@ static Error launch_stream3(CodeState &cs, const DevProps &prop, const uint8_t *
     using S = bs::Shape<9, 3>;
     const clay_code_t &c = cs.code;
     if (c.k != 9 || c.m != 3 || c.d != 11 || sc < 16 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
-    for (int p = 0; p < 3; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    if (Error e = rs_matches<S, 3>(cs)) return e;
     const uint32_t W = 512;
     bs::Enc3Args a{};
     a.sc = sc;
@@ -1458,26 +1517,15 @@ static Error launch_bs_encode1(CodeState &cs, const DevProps &prop, const uint8_
     const clay_code_t &c = cs.code;
     const int W = bs_decode1_tile(int(c.k), int(c.m));  // the line kernels' tile (same lane map)
     if (!W || c.d != c.k + c.m - 1 || c.nu != 0 || sc == 0) return Error{};
-    using S = bs::Shape<4, 2>;
-    for (int p = 0; p < 2; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    if (Error e = rs_matches<bs::Shape<4, 2>, 2>(cs)) return e;
     for (size_t s = 0; s < n_stripes; s++) {
         bs::Enc1Args a{};
-        bool bt = sc % 8 != 0;
-        for (size_t i = 0; i < c.k; i++) {
-            a.data[i] = data[s * c.k + i];
-            bt |= (reinterpret_cast<uintptr_t>(a.data[i]) & 7u) != 0;
-        }
-        for (size_t x = 0; x < c.m; x++) {
-            a.par[x] = par[s * c.m + x];
-            bt |= (reinterpret_cast<uintptr_t>(a.par[x]) & 7u) != 0;
-        }
+        for (size_t i = 0; i < c.k; i++) a.data[i] = data[s * c.k + i];
+        for (size_t x = 0; x < c.m; x++) a.par[x] = par[s * c.m + x];
+        const bool bt = sc % 8 != 0 || misaligned8(a.data, c.k) || misaligned8(a.par, c.m);
         a.sc = sc;
         a.ntiles = uint32_t((sc + size_t(W) - 1) / size_t(W));
-        a.tiles_per_xcd = (a.ntiles + 7) / 8;
-        a.nslots = std::min(a.tiles_per_xcd, uint32_t(std::max(1, prop.cus / 8) * 8));
+        line_slots(a, a.ntiles, prop);
         CLAY_HIP(launch_bs_encode1_kernel(int(c.k), int(c.m), bt, a, stream));
         t_last_launches++;
     }
@@ -1496,13 +1544,7 @@ static Error encode_bitsliced(CodeState &cs, int dev, const uint8_t *const *data
     if (c.d != c.k + c.m - 1) return Error{};
     // the LDS-DMA kernel (stream) needs 8-byte rows: sc % 8 == 0, 8-byte aligned chunks;
     // the v1 kernel takes any sub-chunk size and alignment (byte-granular partial words)
-    bool rows8 = sc % 8 == 0;
-    for (size_t s = 0; s < n_stripes && rows8; s++) {
-        for (size_t i = 0; i < c.k; i++)
-            if (reinterpret_cast<uintptr_t>(data[s * c.k + i]) % 8) rows8 = false;
-        for (size_t i = 0; i < c.m; i++)
-            if (reinterpret_cast<uintptr_t>(par[s * c.m + i]) % 8) rows8 = false;
-    }
+    const bool rows8 = sc % 8 == 0 && !misaligned8(data, n_stripes * c.k) && !misaligned8(par, n_stripes * c.m);
     const DevProps &prop = dev_props(dev);
     Error e;
     const int key = int(c.k * 100 + c.m);
@@ -1571,30 +1613,30 @@ static Error encode_staged(CodeState &cs, DevState &ds, int dev, const uint8_t *
 // cached device table of kMaxBases entries per stripe; U workspace per stripe.
 // Sub-chunks under 4 KiB put several stripes in one block (lps lanes of 16 B per
 // stripe); at most 65,535 blocks of stripes per launch group (grid.y limit).
-// Stripes laid out at fixed strides (clay_encode_device_strided): node i of stripe s at
-// data + s * dstripe + i * dnode, parity j at par + s * pstripe + j * pnode.
-struct Strided {
-    const uint8_t *data;
-    int64_t dnode, dstripe;
-    uint8_t *par;
-    int64_t pnode, pstripe;
-};
+// The stripes' operands come as StripeOperands (stripe_layout.hpp): pointer arrays, or fixed
+// strides (clay_encode_device_strided: node i of stripe s at data + s * dstripe + i * dnode,
+// parity j at par + s * pstripe + j * pnode).
 
 // Batches are launch-bound where a stripe is small: at least kBatchMinStripes stripes of at most
 // kBatchMaxStripeBytes of data (k x chunk) each run as a batch, anything else stripe by stripe.
-// Measured for the encode; the batched decode takes the same thresholds, which
-// nobody has measured for it (its single-launch line batch has no minimum stripe count).
+// Both were measured for the encode ONLY.  The batched decode and the batched
+// repair take the same thresholds, which nobody has measured for them (their single-launch
+// batches have no minimum stripe count).
 constexpr size_t kBatchMinStripes = 4;
 constexpr size_t kBatchMaxStripeBytes = size_t(4) << 20;
 
-// A cached plan (encode or decode: the executor only sees operand bases) over a batch of stripes:
-// one k_gexec launch per plan level for all of them.  `bases`: the plan's bound operand bases
-// (internal node indices); ptr_of(b, s): base b's pointer in stripe s.  `strided`: the pointers
-// are affine in s by construction (no scan).  *launches += the launches issued.
-template <class PtrOf>
-static Error run_plan_batch(CodeState &cs, DevState &ds, int dev, const Plan &pl, const std::vector<size_t> &bases,
-                            const PtrOf &ptr_of, bool strided, size_t n_stripes, size_t chunk, hipStream_t stream,
-                            size_t *launches_out) {
+// An operand base of a plan (an index into ExecPtrs) bound to operand i of a family
+struct BoundBase {
+    size_t base;
+    const StripeOperands *ops;
+    size_t i;
+};
+
+// A cached plan (encode, decode or repair: the executor only sees operand bases) over a batch of
+// stripes: one k_gexec launch per plan level for all of them.  `bases`: the plan's bound operand
+// bases.  *launches += the launches issued.
+static Error run_plan_batch(CodeState &cs, DevState &ds, int dev, const Plan &pl, const std::vector<BoundBase> &bases,
+                            size_t n_stripes, size_t chunk, hipStream_t stream, size_t *launches_out) {
     const clay_code_t &c = cs.code;
     const uint32_t tn = uint32_t(c.q * c.t);
     CodeState::DevGrouped g{};
@@ -1619,17 +1661,9 @@ static Error run_plan_batch(CodeState &cs, DevState &ds, int dev, const Plan &pl
         ExecStride S{};
         bool affine = true;
         for (size_t bi = 0; bi < bases.size() && affine; bi++) {
-            const size_t base = bases[bi];
-            uint8_t *p0 = ptr_of(base, s0);
-            if (strided) {  // strided layout: affine by construction
-                P.p[base] = p0;
-                S.s[base] = int64_t(ptr_of(base, s0 + 1) - p0);
-                continue;
-            }
-            const int64_t st = ns > 1 ? int64_t(ptr_of(base, s0 + 1) - p0) : 0;
-            for (size_t s = 2; s < ns && affine; s++) affine = ptr_of(base, s0 + s) == p0 + int64_t(s) * st;
-            P.p[base] = p0;
-            S.s[base] = st;
+            const BoundBase &b = bases[bi];
+            affine = uniform_stride(*b.ops, s0, ns, &b.i, 1, &S.s[b.base]);
+            P.p[b.base] = b.ops->at(s0, b.i);
         }
         if (ws.l) {
             P.p[2 * tn] = ws.ptr();
@@ -1641,7 +1675,7 @@ static Error run_plan_batch(CodeState &cs, DevState &ds, int dev, const Plan &pl
             std::vector<uint8_t *> tab(ns * kMaxBases, nullptr);
             for (size_t s = 0; s < ns; s++) {
                 uint8_t **t = &tab[s * kMaxBases];
-                for (size_t base : bases) t[base] = ptr_of(base, s0 + s);
+                for (const BoundBase &b : bases) t[b.base] = b.ops->at(s0 + s, b.i);
                 if (ws.l) t[2 * tn] = ws.ptr() + s * tn * chunk;
             }
             e = ptr_table(ds, tab, stream, &pt);
@@ -1668,25 +1702,17 @@ static Error run_plan_batch(CodeState &cs, DevState &ds, int dev, const Plan &pl
     return Error{};
 }
 
-static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const uint8_t *const *data,
-                                 uint8_t *const *par, size_t n_stripes, size_t chunk, hipStream_t stream,
-                                 const Strided *sd) {
+static Error encode_staged_batch(CodeState &cs, DevState &ds, int dev, const StripeOperands &data,
+                                 const StripeOperands &par, size_t n_stripes, size_t chunk, hipStream_t stream) {
     const clay_code_t &c = cs.code;
     const Plan *plp = nullptr;
     Error e = encode_plan(cs, &plp);
     if (e) return e;
-    std::vector<size_t> bases;
-    for (size_t i = 0; i < c.k; i++) bases.push_back(i);
-    for (size_t i = 0; i < c.m; i++) bases.push_back(c.k + c.nu + i);
-    auto ptr_of = [&](size_t b, size_t s) -> uint8_t * {
-        if (b < c.k)
-            return sd ? const_cast<uint8_t *>(sd->data) + int64_t(s) * sd->dstripe + int64_t(b) * sd->dnode
-                      : const_cast<uint8_t *>(data[s * c.k + b]);
-        const size_t j = b - c.k - c.nu;
-        return sd ? sd->par + int64_t(s) * sd->pstripe + int64_t(j) * sd->pnode : par[s * c.m + j];
-    };
+    std::vector<BoundBase> bases;
+    for (size_t i = 0; i < c.k; i++) bases.push_back({i, &data, i});
+    for (size_t i = 0; i < c.m; i++) bases.push_back({c.k + c.nu + i, &par, i});
     size_t launches = 0;
-    e = run_plan_batch(cs, ds, dev, *plp, bases, ptr_of, sd != nullptr, n_stripes, chunk, stream, &launches);
+    e = run_plan_batch(cs, ds, dev, *plp, bases, n_stripes, chunk, stream, &launches);
     if (e) return e;
     t_last_launches += launches;
     t_last_path = "staged-batch";
@@ -1700,10 +1726,7 @@ static Error launch_bs_batch(CodeState &cs, int dev, const uint8_t *const *data0
                              int64_t sdata, int64_t spar, size_t ns, size_t sc, hipStream_t stream, bool *done) {
     using Kn = bs::BsKernel<KD, M, PG>;
     using S = typename Kn::S;
-    for (int p = 0; p < M; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    if (Error e = rs_matches<S, M>(cs)) return e;
     const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
     // sub-chunks well under a tile would leave most lanes idle: the staged batch packs them
     if (sc < uint64_t(Kn::W) / 2 || ntiles * ns >= 0xFFFFFFFFull) return Error{};
@@ -1717,11 +1740,8 @@ static Error launch_bs_batch(CodeState &cs, int dev, const uint8_t *const *data0
         e.nstripes = uint32_t(ns);
         e.sdata = sdata;
         e.spar = spar;
-        e.tiles_per_xcd = uint32_t((ntiles * ns + 7) / 8);
-        e.nslots = std::min(e.tiles_per_xcd, uint32_t(std::max(1, dev_props(dev).cus / 8) * 8));
-        bool bt1 = sc % 8 != 0 || (sdata & 7) != 0 || (spar & 7) != 0;
-        for (int i = 0; i < KD; i++) bt1 |= (reinterpret_cast<uintptr_t>(e.data[i]) & 7u) != 0;
-        for (int x = 0; x < M; x++) bt1 |= (reinterpret_cast<uintptr_t>(e.par[x]) & 7u) != 0;
+        line_slots(e, ntiles * ns, dev_props(dev));
+        const bool bt1 = sc % 8 != 0 || misaligned8(e.data, KD, sdata) || misaligned8(e.par, M, spar);
         CLAY_HIP(launch_bs_encode1_kernel(KD, M, bt1, e, stream));
         t_last_launches++;
         char buf1[64];
@@ -1742,9 +1762,7 @@ static Error launch_bs_batch(CodeState &cs, int dev, const uint8_t *const *data0
     a.tiles_per_xcd = uint32_t((ntiles * ns + 7) / 8);
     const uint32_t max_slots = uint32_t(std::max(1, dev_props(dev).raw.multiProcessorCount / 8) * per_cu);
     a.nslots = std::min(max_slots, a.tiles_per_xcd);
-    bool bt = sc % 8 != 0 || (sdata & 7) != 0 || (spar & 7) != 0;  // byte tails
-    for (int i = 0; i < KD; i++) bt |= (reinterpret_cast<uintptr_t>(a.data[i]) & 7u) != 0;
-    for (int x = 0; x < M; x++) bt |= (reinterpret_cast<uintptr_t>(a.par[x]) & 7u) != 0;
+    const bool bt = sc % 8 != 0 || misaligned8(a.data, KD, sdata) || misaligned8(a.par, M, spar);  // byte tails
     if (bt) bs::k_bs_encode<KD, M, PG, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
     else bs::k_bs_encode<KD, M, PG><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
     CLAY_HIP(hipGetLastError());
@@ -1755,35 +1773,20 @@ static Error launch_bs_batch(CodeState &cs, int dev, const uint8_t *const *data0
     *done = true;
     return Error{};
 }
-static Error encode_bs_batch(CodeState &cs, int dev, const uint8_t *const *data, uint8_t *const *par, size_t ns,
-                             size_t chunk, hipStream_t stream, const Strided *sd, bool *done) {
+static Error encode_bs_batch(CodeState &cs, int dev, const StripeOperands &data, const StripeOperands &par, size_t ns,
+                             size_t chunk, hipStream_t stream, bool *done) {
     *done = false;
     const clay_code_t &c = cs.code;
     const size_t sc = chunk / c.sub_chunk_no;
     const int key = int(c.k * 100 + c.m);
     if (c.d != c.k + c.m - 1 || !(key == 402 || key == 804 || key == 903 || key == 603)) return Error{};
     // stripe-0 pointers and one stride for all data nodes, one for all parity nodes
-    std::vector<const uint8_t *> d0(c.k);
-    std::vector<uint8_t *> p0(c.m);
     int64_t sdata = 0, spar = 0;
-    auto dptr = [&](size_t s, size_t i) -> const uint8_t * {
-        return sd ? sd->data + int64_t(s) * sd->dstripe + int64_t(i) * sd->dnode : data[s * c.k + i];
-    };
-    auto pptr = [&](size_t s, size_t i) -> uint8_t * {
-        return sd ? sd->par + int64_t(s) * sd->pstripe + int64_t(i) * sd->pnode : par[s * c.m + i];
-    };
-    sdata = int64_t(dptr(1, 0) - dptr(0, 0));
-    spar = int64_t(pptr(1, 0) - pptr(0, 0));
-    for (size_t i = 0; i < c.k; i++) d0[i] = dptr(0, i);
-    for (size_t i = 0; i < c.m; i++) p0[i] = pptr(0, i);
-    if (!sd) {
-        for (size_t s = 0; s < ns; s++) {
-            for (size_t i = 0; i < c.k; i++)
-                if (dptr(s, i) != d0[i] + int64_t(s) * sdata) return Error{};
-            for (size_t i = 0; i < c.m; i++)
-                if (pptr(s, i) != p0[i] + int64_t(s) * spar) return Error{};
-        }
-    }
+    if (!uniform_stride(data, 0, ns, nullptr, c.k, &sdata) || !uniform_stride(par, 0, ns, nullptr, c.m, &spar))
+        return Error{};
+    std::vector<uint8_t *> d0(c.k), p0(c.m);
+    data.stripe_ptrs(0, d0.data());
+    par.stripe_ptrs(0, p0.data());
     switch (key) {
     case 402: return launch_bs_batch<4, 2, 64>(cs, dev, d0.data(), p0.data(), sdata, spar, ns, sc, stream, done);
     case 804: return launch_bs_batch<8, 4, 8>(cs, dev, d0.data(), p0.data(), sdata, spar, ns, sc, stream, done);
@@ -1792,28 +1795,32 @@ static Error encode_bs_batch(CodeState &cs, int dev, const uint8_t *const *data,
     }
 }
 
-static Error encode_device_impl(const clay_code_t *code, const uint8_t *const *data, uint8_t *const *par,
-                                size_t n_stripes, size_t chunk, int dev, void *stream, const Strided *sd = nullptr) {
+// data / par: the k data and m parity operands of every stripe, both in the same form (their
+// `per` is set here, once the code is known to be one)
+static Error encode_device_impl(const clay_code_t *code, StripeOperands data, StripeOperands par, size_t n_stripes,
+                                size_t chunk, int dev, void *stream) {
     Error e = check_code(code);
     if (e) return e;
-    if (sd ? (!sd->data || !sd->par) : (!data || !par))
+    data.per = code->k;
+    par.per = code->m;
+    if (data.null() || par.null())
         return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
     if (chunk == 0 || chunk % code->sub_chunk_no != 0)
         return make_error(CLAY_ERR_INVALID_CHUNK_SIZE, code->sub_chunk_no, chunk, 0,
                           "Invalid chunk size: expected divisible by %zu, got %zu", code->sub_chunk_no, chunk);
-    if (!sd) {
+    if (!data.strided) {
         for (size_t i = 0; i < n_stripes * code->k; i++)
-            if (!data[i]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null data chunk");
+            if (!data.ptrs[i]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null data chunk");
         for (size_t i = 0; i < n_stripes * code->m; i++)
-            if (!par[i]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null parity chunk");
+            if (!par.ptrs[i]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null parity chunk");
     }
     if (n_stripes == 0) return Error{};
     t_last_launches = 0;
-    DevState *ds;
-    e = dev_state(dev, &ds);
+    Opened o;
+    e = o.open(*code, dev);
     if (e) return e;
-    DeviceGuard g(dev);
-    CodeState &cs = *code_state(*code);
+    DevState *ds = o.ds;
+    CodeState &cs = *o.cs;
     if (cs.rs.init_err)
         return make_error(CLAY_ERR_RECONSTRUCTION_FAILED, 0, 0, 0, "RS reconstruction failed: RS init failed: %s",
                           rs_error_name(cs.rs.init_err));
@@ -1825,35 +1832,37 @@ static Error encode_device_impl(const clay_code_t *code, const uint8_t *const *d
     if (mode == kModeAuto && n_stripes >= kBatchMinStripes && code->k * chunk <= kBatchMaxStripeBytes &&
         code->q * code->t <= size_t(kMaxTn)) {
         bool done = false;
-        e = encode_bs_batch(cs, dev, data, par, n_stripes, chunk, st, sd, &done);
+        e = encode_bs_batch(cs, dev, data, par, n_stripes, chunk, st, &done);
         if (e || done) return e;
-        return encode_staged_batch(cs, *ds, dev, data, par, n_stripes, chunk, st, sd);
+        return encode_staged_batch(cs, *ds, dev, data, par, n_stripes, chunk, st);
     }
-    std::vector<const uint8_t *> dv;
-    std::vector<uint8_t *> pv;
-    if (sd) {  // per-stripe kernels below take pointer arrays
+    // the per-stripe kernels below take pointer arrays
+    std::vector<uint8_t *> dv, pv;
+    if (data.strided) {
+        dv.resize(n_stripes * code->k);
+        pv.resize(n_stripes * code->m);
         for (size_t s = 0; s < n_stripes; s++) {
-            for (size_t i = 0; i < code->k; i++) dv.push_back(sd->data + int64_t(s) * sd->dstripe + int64_t(i) * sd->dnode);
-            for (size_t i = 0; i < code->m; i++) pv.push_back(sd->par + int64_t(s) * sd->pstripe + int64_t(i) * sd->pnode);
+            data.stripe_ptrs(s, &dv[s * code->k]);
+            par.stripe_ptrs(s, &pv[s * code->m]);
         }
-        data = dv.data();
-        par = pv.data();
     }
+    const uint8_t *const *dp = data.strided ? dv.data() : data.ptrs;
+    uint8_t *const *pp = par.strided ? pv.data() : par.ptrs;
     if (mode == kModeAuto || mode >= kModeBs) {
         bool done = false;
-        e = encode_bitsliced(cs, dev, data, par, n_stripes, chunk, st, mode, tile, &done);
+        e = encode_bitsliced(cs, dev, dp, pp, n_stripes, chunk, st, mode, tile, &done);
         if (e || done) return e;
         if (mode >= kModeBs)
             return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced encode kernel does not support this code/alignment");
     }
     if (mode == kModeAuto || mode == kModeFused) {
         bool done = false;
-        e = encode_fused(cs, *ds, dev, data, par, n_stripes, chunk, st, &done);
+        e = encode_fused(cs, *ds, dev, dp, pp, n_stripes, chunk, st, &done);
         if (e || done) return e;
         if (mode == kModeFused)
             return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "fused encode kernel does not support this code/alignment");
     }
-    return encode_staged(cs, *ds, dev, data, par, n_stripes, chunk, st);
+    return encode_staged(cs, *ds, dev, dp, pp, n_stripes, chunk, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1865,6 +1874,22 @@ static Error encode_device_impl(const clay_code_t *code, const uint8_t *const *d
 // Shared by the streaming decodes: pattern checks, RS rows used, H_K^-1, the v_perm tables of
 // its rows and of A_i = H_K^-1 gamma H_i, the node loads of a tile.  *ok = false: not eligible
 // (per_sec_max: the most erasures one y-section may hold).
+// Erasures per y-section of a q = 4, t = 4 code (`erased` per internal node)
+struct SectionErasures {
+    int per[4] = {0, 0, 0, 0};
+    int nsec = 0;  // sections with an erasure
+    int most = 0;  // the first section with the most erasures
+};
+static SectionErasures section_erasures(const std::vector<uint8_t> &erased) {
+    SectionErasures se;
+    for (size_t i = 0; i < 16 && i < erased.size(); i++) se.per[i / 4] += erased[i] ? 1 : 0;
+    for (int y = 0; y < 4; y++) {
+        if (se.per[y] > se.per[se.most]) se.most = y;
+        se.nsec += se.per[y] ? 1 : 0;
+    }
+    return se;
+}
+
 template <int KD>
 static Error dec_setup(CodeState &cs, const uint8_t *const *cin, uint8_t *const *cout, const std::vector<uint8_t> &erased,
                        size_t sc, int per_sec_max, bs::DecArgs &a, std::vector<uint32_t> &tabs, bool *ok,
@@ -1879,24 +1904,13 @@ static Error dec_setup(CodeState &cs, const uint8_t *const *cin, uint8_t *const 
     if ((!any_sc && sc % 8) || sc < 512 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
     const GF &gf = GF::get();
     std::vector<int> E;
-    int per_sec[4] = {0, 0, 0, 0};
     for (int i = 0; i < 16; i++)
-        if (erased[i]) {
-            E.push_back(i);
-            per_sec[i / 4]++;
-        }
+        if (erased[i]) E.push_back(i);
     if (E.empty() || E.size() > 4) return Error{};
-    for (int y = 0; y < 4; y++)
-        if (per_sec[y] > per_sec_max) return Error{};
-    for (int i = 0; i < 16; i++) {
-        if (any_sc) continue;
-        if (cin[i] && reinterpret_cast<uintptr_t>(cin[i]) % 8) return Error{};
-        if (cout[i] && reinterpret_cast<uintptr_t>(cout[i]) % 8) return Error{};
-    }
-    for (int p = 0; p < 4; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    const SectionErasures se = section_erasures(erased);
+    if (se.per[se.most] > per_sec_max) return Error{};
+    if (!any_sc && (misaligned8(cin, 16) || misaligned8(cout, 16))) return Error{};
+    if (Error e = rs_matches<S, 4>(cs)) return e;
     a = bs::DecArgs{};
     a.g2 = -1;
     // RS rows used: the first 12 present shards (reconstruct, decode.rs:374); K = the rest
@@ -2009,14 +2023,9 @@ template <int KD>
 static Error launch_stream_local(CodeState &cs, const DevProps &prop, const uint8_t *const *cin, uint8_t *const *cout,
                                  const std::vector<uint8_t> &erased, size_t sc, hipStream_t stream, bool *done) {
     *done = false;
-    int per_sec[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 16 && i < int(erased.size()); i++) per_sec[i / 4] += erased[i] ? 1 : 0;
-    int G = 0, nsec = 0;
-    for (int y = 0; y < 4; y++) {
-        if (per_sec[y] > per_sec[G]) G = y;
-        nsec += per_sec[y] ? 1 : 0;
-    }
-    if (nsec == 0 || nsec > 2) return Error{};
+    const SectionErasures se = section_erasures(erased);
+    const int *per_sec = se.per, G = se.most;
+    if (se.nsec == 0 || se.nsec > 2) return Error{};
     int g2 = -1;
     for (int y = 0; y < 4; y++)
         if (y != G && per_sec[y]) {
@@ -2053,11 +2062,7 @@ static Error launch_stream_local(CodeState &cs, const DevProps &prop, const uint
     if (e) return e;
     if (w256) {
         // rows of 8-byte multiples at 8-byte-aligned chunks: the 8-byte kernel; else the ANY one
-        bool any = sc % 8 != 0;
-        for (int i = 0; i < 16; i++) {
-            any = any || (cin[i] && reinterpret_cast<uintptr_t>(cin[i]) % 8);
-            any = any || (cout[i] && reinterpret_cast<uintptr_t>(cout[i]) % 8);
-        }
+        const bool any = sc % 8 != 0 || misaligned8(cin, 16) || misaligned8(cout, 16);
         if (any) CLAY_HIP(launch_stream_local256_any_kernel(KD, G, a, stream, prop.dev));
         else CLAY_HIP(launch_stream_local256_kernel(KD, G, a, stream, prop.dev));
         t_last_exec = "stream-local256";
@@ -2208,6 +2213,23 @@ static Error launch_stream_fused2(CodeState &cs, const DevProps &prop, const uin
 int launch_bs_repair_kernel(int k, int m, int y0, const bs::RepArgs &a, hipStream_t stream, int dev, int cus,
                             int stream_mode, int *launches);
 
+// RepArgs of the bit-sliced repair kernels for lost node `lost` (external).  helper_of(in, &p):
+// whether internal node `in` is a helper, and its buffer.  false: a node other than the lost and
+// the shortened ones is no helper (the kernels read every one of them).
+template <class HelperOf>
+static bool rep_args(const clay_code_t &c, size_t lost, const HelperOf &helper_of, uint8_t *out, size_t sc, bool full,
+                     bs::RepArgs *ra) {
+    const size_t lost_int = internal_of(c, lost);
+    bool ok = true;
+    for (size_t in = 0; in < c.q * c.t; in++)
+        if (in != lost_int && !is_shortened(c, in)) ok = helper_of(in, &ra->h[in]) && ok;
+    ra->out = out;
+    ra->sc = sc;
+    ra->x0 = uint32_t(lost_int % c.q);
+    ra->full = full ? 1u : 0u;
+    return ok;
+}
+
 // One erased node with every other node present, in a q = m code (d = n - 1), through
 // clay_decode_device_codeword: when the chunks are one codeword, the erased chunk is the one a repair from all
 // n - 1 helpers rebuilds (the codeword through the k data chunks is unique: decode.rs:31-161 and
@@ -2223,19 +2245,11 @@ static Error decode_by_repair(const clay_code_t &c, const uint8_t *const *chunks
     const size_t tn = c.q * c.t;
     if (c.q != c.m || tn > 16 || !out) return Error{};
     bs::RepArgs ra{};
-    const size_t lost_int = internal_of(c, lost);
-    for (size_t i = 0; i < c.n; i++) {
-        if (i == lost) continue;
-        if (!chunks[i]) return Error{};
-        ra.h[internal_of(c, i)] = chunks[i];
-    }
-    ra.out = out;
-    ra.sc = chunk / c.sub_chunk_no;
-    ra.x0 = uint32_t(lost_int % c.q);
-    ra.full = 1u;
+    auto helper_of = [&](size_t in, const uint8_t **p) { return (*p = chunks[in < c.k ? in : in - c.nu]) != nullptr; };
+    if (!rep_args(c, lost, helper_of, out, chunk / c.sub_chunk_no, true, &ra)) return Error{};
     int nl = 0;
-    const int r = launch_bs_repair_kernel(int(c.k), int(c.m), int(lost_int / c.q), ra, stream, dev, dev_props(dev).cus, 3,
-                                          &nl);
+    const int r = launch_bs_repair_kernel(int(c.k), int(c.m), int(internal_of(c, lost) / c.q), ra, stream, dev,
+                                          dev_props(dev).cus, 3, &nl);
     if (r < 0) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "HIP error: %s", hipGetErrorString(hipError_t(-r)));
     if (r > 0) {
         t_last_launches += nl;
@@ -2248,35 +2262,43 @@ static Error decode_by_repair(const clay_code_t &c, const uint8_t *const *chunks
 // Single erasure of a small q = m code without shortened nodes ((4,2,5), BASELINE config 2) with
 // every other chunk present: k_bs_decode1 (bitslice_line.hpp), the erased node's whole
 // decode_layered as compile-time XOR networks, one launch.
+// batch: the line batch -- that erasure in every one of ns stripes, stripe s = stripe 0's pointers
+// + s * sin (inputs) / s * sout (output): ONE launch of the column-flattened k_bs_decode1 at any
+// sub-chunk size and alignment.  No allocation, no pointer table: capturable unprepared.
 static Error launch_bs_decode1(CodeState &cs, const DevProps &prop, const uint8_t *const *chunks, size_t e,
-                               uint8_t *out, size_t chunk, hipStream_t stream, bool *done) {
+                               uint8_t *out, size_t chunk, hipStream_t stream, bool *done, bool batch = false,
+                               size_t ns = 1, int64_t sin = 0, int64_t sout = 0) {
     *done = false;
     const clay_code_t &c = cs.code;
     const int W = bs_decode1_tile(int(c.k), int(c.m));
     if (!W || c.d != c.k + c.m - 1 || c.nu != 0 || !out || c.q * c.t > 8) return Error{};
     const size_t sc = chunk / c.sub_chunk_no;
     if (sc == 0 || chunk % c.sub_chunk_no) return Error{};
-    using S = bs::Shape<4, 2>;  // the only instantiation (bs_decode1_tile)
-    for (int p = 0; p < 2; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
+    if (Error re = rs_matches<bs::Shape<4, 2>, 2>(cs)) return re;  // the only instantiation (bs_decode1_tile)
+    const uint64_t cps = (uint64_t(sc) + 31) / 32, pg = uint64_t(W) / 32;
+    if (batch && (cps >= 0xFFFFFFFFull || ns >= 0xFFFFFFFFull || cps * ns >= 0xFFFFFFFFull)) return Error{};  // 32-bit columns
     bs::Dec1Args a{};
-    bool bt = sc % 8 != 0 || (reinterpret_cast<uintptr_t>(out) & 7u) != 0;
     for (size_t i = 0; i < c.n; i++) {
         if (i == e) continue;
         if (!chunks[i]) return Error{};
         a.node[internal_of(c, i)] = chunks[i];
-        bt |= (reinterpret_cast<uintptr_t>(chunks[i]) & 7u) != 0;
     }
     a.out = out;
     a.sc = sc;
-    a.ntiles = uint32_t((sc + size_t(W) - 1) / size_t(W));
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nslots = std::min(a.tiles_per_xcd, uint32_t(std::max(1, prop.cus / 8) * 8));
-    CLAY_HIP(launch_bs_decode1_kernel(int(c.k), int(c.m), int(internal_of(c, e)), bt, a, stream));
+    const bool bt = sc % 8 != 0 || misaligned8(&a.out, 1, sout) || misaligned8(a.node, 8, sin);
+    if (batch) {  // tiles of W / 32 columns over all stripes
+        a.cps = uint32_t(cps);
+        a.ncols = uint32_t(cps * ns);
+        a.sin = sin;
+        a.sout = sout;
+        a.ntiles = uint32_t((cps * ns + pg - 1) / pg);
+    } else {  // tiles of W positions
+        a.ntiles = uint32_t((sc + size_t(W) - 1) / size_t(W));
+    }
+    line_slots(a, a.ntiles, prop);
+    CLAY_HIP(launch_bs_decode1_kernel(int(c.k), int(c.m), int(internal_of(c, e)), bt, a, stream, batch));
     t_last_launches += 1;
-    t_last_exec = "bs-decode1";
+    t_last_exec = batch ? "bs-decode1-batch" : "bs-decode1";
     *done = true;
     return Error{};
 }
@@ -2326,18 +2348,13 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
     if (e || nothing) return e;
     const size_t tn = c.q * c.t;
     t_last_launches = 0;
-    DevState *ds;
-    e = dev_state(dev, &ds);
+    Opened o;
+    e = o.open_max_tn(c, dev);
     if (e) return e;
-    DeviceGuard g(dev);
-    CodeState &cs = *code_state(c);
-    if (tn > size_t(kMaxTn))
-        return make_error(CLAY_ERR_DEVICE, tn, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
-    std::vector<uint8_t> key(erased);
-    key.insert(key.end(), want.begin(), want.end());
+    DevState *ds = o.ds;
+    CodeState &cs = *o.cs;
     const Plan *plan = nullptr;
-    e = cached_plan(cs, cs.dec, key, [&](std::unique_ptr<Plan> &p) { return plan_decode(c, cs.rs, erased, want, p); },
-                    &plan);
+    e = decode_plan(cs, erased, want, &plan);
     if (e) return e;
     ExecPtrs P{};
     for (size_t i = 0; i < c.n; i++) {
@@ -2377,14 +2394,8 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
     // 0.48-0.53 ms vs 0.50-0.54 on the 64-byte local decode (profiles/r06/decode/two_small_*)
     bool f2_first = false;
     if (try_f2 && try_local && n_erased == 3 && tn == 16) {
-        int per[4] = {0, 0, 0, 0};
-        for (size_t in = 0; in < tn; in++) per[in / 4] += erased[in] ? 1 : 0;
-        int nsec = 0, mx = 0;
-        for (int y = 0; y < 4; y++) {
-            nsec += per[y] ? 1 : 0;
-            mx = std::max(mx, per[y]);
-        }
-        f2_first = nsec == 2 && mx == 2;
+        const SectionErasures se = section_erasures(erased);
+        f2_first = se.nsec == 2 && se.per[se.most] == 2;
     }
     if ((try_local || try_f2) && tn == 16) {
         const uint8_t *cin[16] = {};
@@ -2398,196 +2409,123 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
         const DevProps &prop = dev_props(dev);
         const size_t sc = chunk / c.sub_chunk_no;
         hipStream_t st = static_cast<hipStream_t>(stream);
-        if (f2_first) {
-            if (c.k == 10) e = launch_stream_fused2<10>(cs, prop, cin, cout, erased, sc, st, &done);
-            else if (c.k == 9) e = launch_stream_fused2<9>(cs, prop, cin, cout, erased, sc, st, &done);
-            if (e || done) return e;
-        }
+        auto fused2 = [&] {
+            return c.k == 10 ? launch_stream_fused2<10>(cs, prop, cin, cout, erased, sc, st, &done)
+                 : c.k == 9  ? launch_stream_fused2<9>(cs, prop, cin, cout, erased, sc, st, &done)
+                             : Error{};
+        };
+        if (f2_first) e = fused2();
+        if (e || done) return e;
         if (try_local) {
             if (c.k == 10) e = launch_stream_local<10>(cs, prop, cin, cout, erased, sc, st, &done);
             else if (c.k == 9) e = launch_stream_local<9>(cs, prop, cin, cout, erased, sc, st, &done);
             if (e || done) return e;
         }
-        if (try_f2 && !f2_first) {
-            if (c.k == 10) e = launch_stream_fused2<10>(cs, prop, cin, cout, erased, sc, st, &done);
-            else if (c.k == 9) e = launch_stream_fused2<9>(cs, prop, cin, cout, erased, sc, st, &done);
-            if (e || done) return e;
-        }
+        if (try_f2 && !f2_first) e = fused2();
+        if (e || done) return e;
     }
     return run_plan(cs, *plan, dev, *ds, static_cast<hipStream_t>(stream), P, chunk / c.sub_chunk_no, chunk);
 }
 
 // ---- batched decode: n_stripes stripes with the same erasure set (clay_decode_device_strided /
 // clay_decode_device_batch) ----
-// Stripes at fixed strides: node i of stripe s at chunks + s * stripe + i * node, the rebuilt
-// node e at out + s * ostripe + e * onode.
-struct DecStrided {
-    const uint8_t *chunks;
-    int64_t node, stripe;
-    uint8_t *out;
-    int64_t onode, ostripe;
-};
-
-// Line batch: one erasure of (4,2,5) in every stripe, stripe s = stripe 0's pointers + s * sin
-// (inputs) / s * sout (output): ONE launch of the column-flattened k_bs_decode1 (bitslice_line.hpp)
-// at any sub-chunk size and alignment.  No allocation, no pointer table: capturable unprepared.
-static Error launch_bs_decode1_batch(CodeState &cs, const DevProps &prop, const uint8_t *const *chunks0, int64_t sin,
-                                     size_t e, uint8_t *out0, int64_t sout, size_t ns, size_t chunk,
-                                     hipStream_t stream, bool *done) {
-    *done = false;
-    const clay_code_t &c = cs.code;
-    const int W = bs_decode1_tile(int(c.k), int(c.m));
-    if (!W || c.d != c.k + c.m - 1 || c.nu != 0 || !out0 || c.q * c.t > 8) return Error{};
-    const size_t sc = chunk / c.sub_chunk_no;
-    if (sc == 0 || chunk % c.sub_chunk_no) return Error{};
-    using S = bs::Shape<4, 2>;  // the only instantiation (bs_decode1_tile)
-    for (int p = 0; p < 2; p++)
-        for (int i = 0; i < S::K; i++)
-            if (S::RS.g[p][i] != cs.rs.gen[(S::K + p) * S::K + i])
-                return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "bit-sliced RS table mismatch");
-    const uint64_t cps = (uint64_t(sc) + 31) / 32, pg = uint64_t(W) / 32;
-    if (cps >= 0xFFFFFFFFull || ns >= 0xFFFFFFFFull || cps * ns >= 0xFFFFFFFFull) return Error{};  // 32-bit columns
-    bs::Dec1Args a{};
-    bool bt = sc % 8 != 0 || (reinterpret_cast<uintptr_t>(out0) & 7u) != 0 || (sin & 7) != 0 || (sout & 7) != 0;
-    for (size_t i = 0; i < c.n; i++) {
-        if (i == e) continue;
-        if (!chunks0[i]) return Error{};
-        a.node[internal_of(c, i)] = chunks0[i];
-        bt |= (reinterpret_cast<uintptr_t>(chunks0[i]) & 7u) != 0;
-    }
-    a.out = out0;
-    a.sc = sc;
-    a.cps = uint32_t(cps);
-    a.ncols = uint32_t(cps * ns);
-    a.sin = sin;
-    a.sout = sout;
-    a.ntiles = uint32_t((cps * ns + pg - 1) / pg);
-    a.tiles_per_xcd = (a.ntiles + 7) / 8;
-    a.nslots = std::min(a.tiles_per_xcd, uint32_t(std::max(1, prop.cus / 8) * 8));
-    CLAY_HIP(launch_bs_decode1_kernel(int(c.k), int(c.m), int(internal_of(c, e)), bt, a, stream, true));
-    t_last_launches += 1;
-    t_last_exec = "bs-decode1-batch";
-    *done = true;
-    return Error{};
-}
-
-// chunks / outs: n_stripes x n pointer arrays (sd == nullptr), or the strided layout `sd`.
-static Error decode_batch_impl(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
-                               uint8_t *const *outs, size_t n_stripes, size_t chunk, int dev, void *stream,
-                               const DecStrided *sd) {
+// in / out: the n chunks and the n output buffers of every stripe, both in the same form.  Pointer
+// arrays: NULL where absent / not wanted.  Strides (node i of stripe s at chunks + s * stripe +
+// i * node, the rebuilt node e at out + s * ostripe + e * onode): every node outside `erasures` is
+// available and every erased one is rebuilt, so the inputs of erased nodes and the outputs of
+// present ones are NULL.
+static Error decode_batch_impl(const clay_code_t *code, StripeOperands in, const size_t *er, size_t ner,
+                               StripeOperands out, size_t n_stripes, size_t chunk, int dev, void *stream) {
     Error e = check_code(code);
     if (e) return e;
     const clay_code_t &c = *code;
-    if (sd ? (!sd->chunks || !sd->out) : (!chunks || !outs))
+    in.per = out.per = c.n;
+    if (in.null() || out.null())
         return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
     if (ner && !er) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null erasure array");
-    if (!sd && n_stripes == 0) return Error{};  // no stripe to take the NULL pattern from
-    // stripe 0's pointer arrays: the strided form has every node outside `erasures` available and
-    // rebuilds every erased one
-    std::vector<const uint8_t *> c0(c.n, nullptr);
-    std::vector<uint8_t *> o0(c.n, nullptr);
-    std::vector<uint8_t> gone(c.n, 0);
-    if (sd)
+    if (!in.strided && n_stripes == 0) return Error{};  // no stripe to take the NULL pattern from
+    std::vector<uint8_t> gone(c.n, 0), kept(c.n, 1);
+    if (in.strided) {
         for (size_t i = 0; i < ner; i++)
-            if (er[i] < c.n) gone[er[i]] = 1;
-    auto cptr = [&](size_t s, size_t i) -> const uint8_t * {
-        if (!sd) return chunks[s * c.n + i];
-        return gone[i] ? nullptr : sd->chunks + int64_t(s) * sd->stripe + int64_t(i) * sd->node;
-    };
-    auto optr = [&](size_t s, size_t i) -> uint8_t * {
-        if (!sd) return outs[s * c.n + i];
-        return gone[i] ? sd->out + int64_t(s) * sd->ostripe + int64_t(i) * sd->onode : nullptr;
-    };
-    for (size_t i = 0; i < c.n; i++) {
-        c0[i] = cptr(0, i);
-        o0[i] = optr(0, i);
+            if (er[i] < c.n) {
+                gone[er[i]] = 1;
+                kept[er[i]] = 0;
+            }
+        in.absent = gone.data();
+        out.absent = kept.data();
     }
+    // stripe 0's pointer arrays
+    std::vector<uint8_t *> c0(c.n), o0(c.n);
+    in.stripe_ptrs(0, c0.data());
+    out.stripe_ptrs(0, o0.data());
     std::vector<uint8_t> erased, want;
     size_t n_present = 0;
     bool nothing = false;
     e = decode_check(c, c0.data(), er, ner, o0.data(), chunk, erased, want, &n_present, &nothing);
     if (e || nothing) return e;
-    if (!sd)
+    if (!in.strided)
         for (size_t s = 1; s < n_stripes; s++)
             for (size_t i = 0; i < c.n; i++)
-                if (!chunks[s * c.n + i] != !c0[i] || (!c0[i] && !outs[s * c.n + i] != !o0[i]))
+                if (!in.at(s, i) != !c0[i] || (!c0[i] && !out.at(s, i) != !o0[i]))
                     return make_error(CLAY_ERR_INVALID_PARAMETERS, s, i, 0,
                                       "Invalid parameters: stripe %zu differs from stripe 0 in the NULL pattern at node %zu",
                                       s, i);
     if (n_stripes == 0) return Error{};
     const size_t tn = c.q * c.t;
     t_last_launches = 0;
-    DevState *ds;
-    e = dev_state(dev, &ds);
+    Opened o;
+    e = o.open_max_tn(c, dev);
     if (e) return e;
-    DeviceGuard g(dev);
-    CodeState &cs = *code_state(c);
-    if (tn > size_t(kMaxTn))
-        return make_error(CLAY_ERR_DEVICE, tn, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
+    DevState *ds = o.ds;
+    CodeState &cs = *o.cs;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int xmode = g_exec_mode.load(std::memory_order_relaxed);
     if (c.k * chunk <= kBatchMaxStripeBytes) {
         size_t n_erased = 0;
-        for (size_t in = 0; in < tn; in++) n_erased += erased[in] && !(in >= c.k && in < c.k + c.nu) ? 1 : 0;
+        for (size_t b = 0; b < tn; b++) n_erased += erased[b] && !is_shortened(c, b) ? 1 : 0;
         // line batch: one erasure of (4,2,5), every other chunk present, auto / "stream", the
         // stripes at uniform strides (the strided form, or pointer arrays that are rows of one
         // buffer); one launch for any number of stripes
         if ((xmode == kExecAuto || xmode == kExecStream) && n_erased == 1 && ner == 1 && n_present + 1 == c.n &&
             bs_decode1_tile(int(c.k), int(c.m)) && o0[er[0]]) {
-            const size_t i0 = er[0] == 0 ? 1 : 0;  // a present node
-            const int64_t sin = sd ? sd->stripe : n_stripes > 1 ? int64_t(cptr(1, i0) - c0[i0]) : 0;
-            const int64_t sout = sd ? sd->ostripe : n_stripes > 1 ? int64_t(optr(1, er[0]) - o0[er[0]]) : 0;
-            bool uniform = true;
-            if (!sd)
-                for (size_t s = 1; s < n_stripes && uniform; s++) {
-                    for (size_t i = 0; i < c.n && uniform; i++)
-                        if (c0[i]) uniform = cptr(s, i) == c0[i] + int64_t(s) * sin;
-                    uniform = uniform && optr(s, er[0]) == o0[er[0]] + int64_t(s) * sout;
-                }
-            if (uniform) {
+            // every present node (the first one gives the stride) and the one output
+            std::vector<size_t> present;
+            for (size_t i = 0; i < c.n; i++)
+                if (i != er[0]) present.push_back(i);
+            int64_t sin = 0, sout = 0;
+            if (uniform_stride(in, 0, n_stripes, present.data(), present.size(), &sin) &&
+                uniform_stride(out, 0, n_stripes, &er[0], 1, &sout)) {
                 bool done = false;
-                e = launch_bs_decode1_batch(cs, dev_props(dev), c0.data(), sin, er[0], o0[er[0]], sout, n_stripes, chunk,
-                                            st, &done);
+                e = launch_bs_decode1(cs, dev_props(dev), c0.data(), er[0], o0[er[0]], chunk, st, &done, true, n_stripes,
+                                      sin, sout);
                 if (e || done) return e;
             }
         }
     }
     if (n_stripes >= kBatchMinStripes && c.k * chunk <= kBatchMaxStripeBytes) {
         // staged batch: the cached decode plan, one k_gexec launch per level for the whole batch
-        std::vector<uint8_t> key(erased);
-        key.insert(key.end(), want.begin(), want.end());
         const Plan *plan = nullptr;
-        e = cached_plan(cs, cs.dec, key, [&](std::unique_ptr<Plan> &p) { return plan_decode(c, cs.rs, erased, want, p); },
-                        &plan);
+        e = decode_plan(cs, erased, want, &plan);
         if (e) return e;
-        std::vector<size_t> bases, ext(tn, 0);
+        std::vector<BoundBase> bases;
         for (size_t i = 0; i < c.n; i++) {
-            const size_t in = internal_of(c, i);
-            if (c0[i] || (want[in] && o0[i])) {
-                bases.push_back(in);
-                ext[in] = i;
-            }
+            const size_t b = internal_of(c, i);
+            if (c0[i]) bases.push_back({b, &in, i});
+            else if (want[b] && o0[i]) bases.push_back({b, &out, i});
         }
-        auto ptr_of = [&](size_t b, size_t s) -> uint8_t * {
-            const size_t i = ext[b];
-            return c0[i] ? const_cast<uint8_t *>(cptr(s, i)) : optr(s, i);
-        };
         size_t launches = 0;
-        e = run_plan_batch(cs, *ds, dev, *plan, bases, ptr_of, sd != nullptr, n_stripes, chunk, st, &launches);
+        e = run_plan_batch(cs, *ds, dev, *plan, bases, n_stripes, chunk, st, &launches);
         if (e) return e;
         t_last_launches += launches;
         t_last_exec = "grouped-batch";
         return Error{};
     }
     // few or large stripes: stripe by stripe
-    std::vector<const uint8_t *> cv(c.n);
-    std::vector<uint8_t *> ov(c.n);
+    std::vector<uint8_t *> cv(c.n), ov(c.n);
     size_t launches = 0;
     for (size_t s = 0; s < n_stripes; s++) {
-        for (size_t i = 0; i < c.n; i++) {
-            cv[i] = cptr(s, i);
-            ov[i] = optr(s, i);
-        }
+        in.stripe_ptrs(s, cv.data());
+        out.stripe_ptrs(s, ov.data());
         e = decode_device_impl(code, cv.data(), er, ner, ov.data(), chunk, dev, stream);
         if (e) return e;
         launches += t_last_launches;
@@ -2609,14 +2547,12 @@ static Error repair_device_impl(const clay_code_t *code, size_t lost, const size
     if (e) return e;
     if (!out) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
     t_last_launches = 0;
-    DevState *ds;
-    e = dev_state(dev, &ds);
+    Opened o;
+    e = o.open_max_tn(c, dev);
     if (e) return e;
-    DeviceGuard g(dev);
+    DevState *ds = o.ds;
+    CodeState &cs = *o.cs;
     const size_t tn = c.q * c.t;
-    if (tn > size_t(kMaxTn))
-        return make_error(CLAY_ERR_DEVICE, tn, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
-    CodeState &cs = *code_state(c);
     // bit-sliced single-launch repair (repair_kernel.hpp): q = m codes with every other node a
     // helper (no aloof nodes); auto and "stream" exec modes ((9,3,11) 256 MiB chunks: 0.345-0.357
     // vs 0.39-0.41 ms grouped on the same boxes, profiles/r03/)
@@ -2624,23 +2560,17 @@ static Error repair_device_impl(const clay_code_t *code, size_t lost, const size
     const bool xauto = xm == kExecAuto;
     if ((xauto || xm == kExecStream) && c.q == c.m && tn <= 16 && nh + 1 == c.n) {
         bs::RepArgs ra{};
-        const size_t lost_int = internal_of(c, lost);
-        bool ok = true;
-        for (size_t in = 0; in < tn; in++) {
-            if (in == lost_int || (in >= c.k && in < c.k + c.nu)) continue;
-            if (slot_of[in] < 0) ok = false;
-            else ra.h[in] = bufs[slot_of[in]];
-        }
-        if (ok) {
-            ra.out = out;
-            ra.sc = chunk / c.sub_chunk_no;
-            ra.x0 = uint32_t(lost_int % c.q);
-            ra.full = full ? 1u : 0u;
+        auto helper_of = [&](size_t in, const uint8_t **p) {
+            if (slot_of[in] >= 0) *p = bufs[slot_of[in]];
+            return slot_of[in] >= 0;
+        };
+        if (rep_args(c, lost, helper_of, out, chunk / c.sub_chunk_no, full, &ra)) {
             // streaming variant (LDS-DMA, one workgroup per CU): auto when every CU gets a tile,
             // always in exec mode "stream"
             int nl = 0;
-            const int r = launch_bs_repair_kernel(int(c.k), int(c.m), int(lost_int / c.q), ra, static_cast<hipStream_t>(stream),
-                                                  dev, dev_props(dev).cus, xauto ? 1 : 2, &nl);
+            const int r = launch_bs_repair_kernel(int(c.k), int(c.m), int(internal_of(c, lost) / c.q), ra,
+                                                  static_cast<hipStream_t>(stream), dev, dev_props(dev).cus,
+                                                  xauto ? 1 : 2, &nl);
             if (r < 0) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "HIP error: %s", hipGetErrorString(hipError_t(-r)));
             if (r > 0) {
                 t_last_launches += nl;
@@ -2649,14 +2579,8 @@ static Error repair_device_impl(const clay_code_t *code, size_t lost, const size
             }
         }
     }
-    std::vector<uint8_t> key(hin);
-    key.push_back(uint8_t(lost & 0xFF));
-    key.push_back(uint8_t(lost >> 8));
-    key.push_back(uint8_t(full));
     const Plan *plan = nullptr;
-    e = cached_plan(cs, cs.rep, key,
-                    [&](std::unique_ptr<Plan> &p) { return plan_repair(c, cs.rs, lost, hin, slot_of, sub, p, full); },
-                    &plan);
+    e = repair_plan(cs, lost, hin, slot_of, sub, full, &plan);
     if (e) return e;
     ExecPtrs P{};
     for (size_t in = 0; in < tn; in++)
@@ -2678,21 +2602,13 @@ int launch_bs_repair_batch_kernel(int k, int m, int y0, const bs::RepArgs &a, hi
 // runs while a stripe has under two whole columns (49..63 are not measured).
 constexpr size_t kRepairBatchJfastMaxSc = 63;
 
-// Stripes at fixed strides: the helper buffer of external node i of stripe s at helpers +
-// s * stripe + i * node, the rebuilt chunk at out + s * ostripe.
-struct RepStrided {
-    const uint8_t *helpers;
-    int64_t node, stripe;
-    uint8_t *out;
-    int64_t ostripe;
-};
-
-// bufs: n_stripes x nh helper pointers and outs: n_stripes outputs (sd == nullptr), or the strided
-// layout `sd`.  `full`: helper buffers are whole chunks (clay_repair_device_full_chunks), else the
-// beta repair sub-chunks (clay_repair_device).
-static Error repair_batch_impl(const clay_code_t *code, size_t lost, const size_t *ids, const uint8_t *const *bufs,
-                               size_t nh, bool full, uint8_t *const *outs, size_t n_stripes, size_t chunk, int dev,
-                               void *stream, const RepStrided *sd) {
+// helpers: the nh helper buffers of every stripe, helper slot h being node ids[h]; out: its one
+// output; both in the same form.  Strides: the helper buffer of external node i of stripe s at
+// helpers + s * stripe + i * node (so slot h sits at node ids[h]), the rebuilt chunk at out +
+// s * ostripe.  `full`: helper buffers are whole chunks (clay_repair_device_full_chunks), else
+// the beta repair sub-chunks (clay_repair_device).
+static Error repair_batch_impl(const clay_code_t *code, size_t lost, const size_t *ids, StripeOperands helpers, size_t nh,
+                               bool full, StripeOperands out, size_t n_stripes, size_t chunk, int dev, void *stream) {
     Error e = check_code(code);
     if (e) return e;
     const clay_code_t &c = *code;
@@ -2701,30 +2617,26 @@ static Error repair_batch_impl(const clay_code_t *code, size_t lost, const size_
     std::vector<size_t> sub;
     e = validate_repair(c, lost, ids, nullptr, nh, chunk, hin, slot_of, sub);
     if (e) return e;
-    if (sd ? !sd->helpers : !bufs)
-        return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null helper buffer");
-    if (sd ? !sd->out : !outs) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
-    auto hptr = [&](size_t s, size_t h) -> const uint8_t * {
-        return sd ? sd->helpers + int64_t(s) * sd->stripe + int64_t(ids[h]) * sd->node : bufs[s * nh + h];
-    };
-    auto optr = [&](size_t s) -> uint8_t * { return sd ? sd->out + int64_t(s) * sd->ostripe : outs[s]; };
-    if (!sd)
+    helpers.per = nh;
+    helpers.index = ids;
+    out.per = 1;
+    if (helpers.null()) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null helper buffer");
+    if (out.null()) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
+    if (!helpers.strided)
         for (size_t s = 0; s < n_stripes; s++) {
             for (size_t h = 0; h < nh; h++)
-                if (!bufs[s * nh + h])
+                if (!helpers.at(s, h))
                     return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null helper buffer");
-            if (!outs[s]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
+            if (!out.at(s, 0)) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null output");
         }
     if (n_stripes == 0) return Error{};
     t_last_launches = 0;
-    DevState *ds;
-    e = dev_state(dev, &ds);
+    Opened o;
+    e = o.open_max_tn(c, dev);
     if (e) return e;
-    DeviceGuard g(dev);
+    DevState *ds = o.ds;
+    CodeState &cs = *o.cs;
     const size_t tn = c.q * c.t;
-    if (tn > size_t(kMaxTn))
-        return make_error(CLAY_ERR_DEVICE, tn, 0, 0, "device engine supports at most %d internal nodes", kMaxTn);
-    CodeState &cs = *code_state(c);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int xm = g_exec_mode.load(std::memory_order_relaxed);
     // The thresholds are the encode's (kBatchMinStripes, kBatchMaxStripeBytes: DESIGN.md §4.4), as
@@ -2738,34 +2650,25 @@ static Error repair_batch_impl(const clay_code_t *code, size_t lost, const size_
     // unprepared.
     if ((xm == kExecAuto || xm == kExecStream) && small && c.q == c.m && tn <= 16 && nh + 1 == c.n) {
         bs::RepArgs ra{};
-        const size_t lost_int = internal_of(c, lost);
-        bool ok = true;
-        for (size_t in = 0; in < tn; in++) {
-            if (in == lost_int || (in >= c.k && in < c.k + c.nu)) continue;
-            if (slot_of[in] < 0) ok = false;
-            else ra.h[in] = hptr(0, size_t(slot_of[in]));
-        }
-        const int64_t sin = sd ? sd->stripe : n_stripes > 1 ? int64_t(hptr(1, 0) - hptr(0, 0)) : 0;
-        const int64_t sout = sd ? sd->ostripe : n_stripes > 1 ? int64_t(optr(1) - optr(0)) : 0;
-        if (ok && !sd)
-            for (size_t s = 1; s < n_stripes && ok; s++) {
-                for (size_t h = 0; h < nh && ok; h++) ok = hptr(s, h) == hptr(0, h) + int64_t(s) * sin;
-                ok = ok && optr(s) == optr(0) + int64_t(s) * sout;
-            }
+        auto helper_of = [&](size_t in, const uint8_t **p) {
+            if (slot_of[in] >= 0) *p = helpers.at(0, size_t(slot_of[in]));
+            return slot_of[in] >= 0;
+        };
+        bool ok = rep_args(c, lost, helper_of, out.at(0, 0), sc, full, &ra);
+        // every helper (slot 0 gives the stride) and the output
+        int64_t sin = 0, sout = 0;
+        ok = ok && uniform_stride(helpers, 0, n_stripes, nullptr, nh, &sin) &&
+             uniform_stride(out, 0, n_stripes, nullptr, 1, &sout);
         const uint64_t cps = bs::rep_batch_cps(sc);
         if (cps >= 0xFFFFFFFFull || n_stripes >= 0xFFFFFFFFull || cps * n_stripes >= 0xFFFFFFFFull) ok = false;  // 32-bit columns
         if (ok) {
-            ra.out = optr(0);
-            ra.sc = sc;
-            ra.x0 = uint32_t(lost_int % c.q);
-            ra.full = full ? 1u : 0u;
             ra.cps = uint32_t(cps);
             ra.ncols = uint32_t(cps * n_stripes);
             ra.sin = sin;
             ra.sout = sout;
             const int jt = tuning().repair_batch_jfast;
             const bool jfast = jt < 0 ? sc <= kRepairBatchJfastMaxSc : jt != 0;
-            const int r = launch_bs_repair_batch_kernel(int(c.k), int(c.m), int(lost_int / c.q), ra, st, jfast);
+            const int r = launch_bs_repair_batch_kernel(int(c.k), int(c.m), int(internal_of(c, lost) / c.q), ra, st, jfast);
             if (r < 0) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "HIP error: %s", hipGetErrorString(hipError_t(-r)));
             if (r > 0) {
                 t_last_launches += 1;
@@ -2776,35 +2679,26 @@ static Error repair_batch_impl(const clay_code_t *code, size_t lost, const size_
     }
     if (n_stripes >= kBatchMinStripes && small) {
         // staged batch: the cached repair plan, one k_gexec launch per level for the whole batch
-        std::vector<uint8_t> key(hin);
-        key.push_back(uint8_t(lost & 0xFF));
-        key.push_back(uint8_t(lost >> 8));
-        key.push_back(uint8_t(full));
         const Plan *plan = nullptr;
-        e = cached_plan(cs, cs.rep, key,
-                        [&](std::unique_ptr<Plan> &p) { return plan_repair(c, cs.rs, lost, hin, slot_of, sub, p, full); },
-                        &plan);
+        e = repair_plan(cs, lost, hin, slot_of, sub, full, &plan);
         if (e) return e;
-        std::vector<size_t> bases;
+        std::vector<BoundBase> bases;
         for (size_t in = 0; in < tn; in++)
-            if (slot_of[in] >= 0) bases.push_back(tn + in);
-        bases.push_back(2 * tn + 1);
-        auto ptr_of = [&](size_t b, size_t s) -> uint8_t * {
-            return b == 2 * tn + 1 ? optr(s) : const_cast<uint8_t *>(hptr(s, size_t(slot_of[b - tn])));
-        };
+            if (slot_of[in] >= 0) bases.push_back({tn + in, &helpers, size_t(slot_of[in])});
+        bases.push_back({2 * tn + 1, &out, 0});
         size_t launches = 0;
-        e = run_plan_batch(cs, *ds, dev, *plan, bases, ptr_of, sd != nullptr, n_stripes, chunk, st, &launches);
+        e = run_plan_batch(cs, *ds, dev, *plan, bases, n_stripes, chunk, st, &launches);
         if (e) return e;
         t_last_launches += launches;
         t_last_exec = "grouped-batch";
         return Error{};
     }
     // few or large stripes: stripe by stripe
-    std::vector<const uint8_t *> hv(nh);
+    std::vector<uint8_t *> hv(nh);
     size_t launches = 0;
     for (size_t s = 0; s < n_stripes; s++) {
-        for (size_t h = 0; h < nh; h++) hv[h] = hptr(s, h);
-        e = repair_device_impl(code, lost, ids, hv.data(), nullptr, nh, chunk, optr(s), dev, stream, full);
+        helpers.stripe_ptrs(s, hv.data());
+        e = repair_device_impl(code, lost, ids, hv.data(), nullptr, nh, chunk, out.at(s, 0), dev, stream, full);
         if (e) return e;
         launches += t_last_launches;
     }
@@ -2968,6 +2862,12 @@ static int current_device(Error *e) {
     return d;
 }
 
+// How a C ABI entry point ends: *err cleared, then filled from a failure; 0, or the error's code.
+static int abi_result(clay_error_t *err, const Error &e) {
+    if (err) std::memset(err, 0, sizeof(*err));
+    return e ? report(e, err) : 0;
+}
+
 }  // namespace clay
 
 // ===========================================================================
@@ -3038,26 +2938,23 @@ int clay_minimum_to_repair(const clay_code_t *code, size_t lost, const size_t *a
 
 int clay_encode_device(const clay_code_t *code, const uint8_t *const *data, uint8_t *const *par, size_t chunk,
                        int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = encode_device_impl(code, data, par, 1, chunk, device, stream);
-    return e ? report(e, err) : 0;
+    return abi_result(err, encode_device_impl(code, StripeOperands::from_arrays(data), StripeOperands::from_arrays(par), 1,
+                                              chunk, device, stream));
 }
 
 int clay_encode_device_batch(const clay_code_t *code, const uint8_t *const *data, uint8_t *const *par, size_t ns,
                              size_t chunk, int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = encode_device_impl(code, data, par, ns, chunk, device, stream);
-    return e ? report(e, err) : 0;
+    return abi_result(err, encode_device_impl(code, StripeOperands::from_arrays(data), StripeOperands::from_arrays(par), ns,
+                                              chunk, device, stream));
 }
 
 int clay_encode_device_strided(const clay_code_t *code, const uint8_t *data, int64_t data_node_stride,
                                int64_t data_stripe_stride, uint8_t *parity, int64_t parity_node_stride,
                                int64_t parity_stripe_stride, size_t n_stripes, size_t chunk, int device, void *stream,
                                clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    const Strided sd{data, data_node_stride, data_stripe_stride, parity, parity_node_stride, parity_stripe_stride};
-    Error e = encode_device_impl(code, nullptr, nullptr, n_stripes, chunk, device, stream, &sd);
-    return e ? report(e, err) : 0;
+    return abi_result(err, encode_device_impl(code, StripeOperands::from_strides(data, data_node_stride, data_stripe_stride),
+                                              StripeOperands::from_strides(parity, parity_node_stride, parity_stripe_stride),
+                                              n_stripes, chunk, device, stream));
 }
 
 static Error ygroup_impl(const clay_code_t *code, size_t y, const uint8_t *src, uint8_t *dst, size_t chunk, int dev,
@@ -3092,81 +2989,65 @@ static Error ygroup_impl(const clay_code_t *code, size_t y, const uint8_t *src, 
 
 int clay_chunk_to_ygroup(const clay_code_t *code, size_t y, const uint8_t *chunk, uint8_t *group, size_t chunk_size,
                          int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = ygroup_impl(code, y, chunk, group, chunk_size, device, stream, true);
-    return e ? report(e, err) : 0;
+    return abi_result(err, ygroup_impl(code, y, chunk, group, chunk_size, device, stream, true));
 }
 
 int clay_ygroup_to_chunk(const clay_code_t *code, size_t y, const uint8_t *group, uint8_t *chunk, size_t chunk_size,
                          int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = ygroup_impl(code, y, group, chunk, chunk_size, device, stream, false);
-    return e ? report(e, err) : 0;
+    return abi_result(err, ygroup_impl(code, y, group, chunk, chunk_size, device, stream, false));
 }
 
 int clay_decode_device(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
                        uint8_t *const *outs, size_t chunk, int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = decode_device_impl(code, chunks, er, ner, outs, chunk, device, stream);
-    return e ? report(e, err) : 0;
+    return abi_result(err, decode_device_impl(code, chunks, er, ner, outs, chunk, device, stream));
 }
 
 int clay_decode_device_codeword(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
                                 uint8_t *const *outs, size_t chunk, int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = decode_device_impl(code, chunks, er, ner, outs, chunk, device, stream, true);
-    return e ? report(e, err) : 0;
+    return abi_result(err, decode_device_impl(code, chunks, er, ner, outs, chunk, device, stream, true));
 }
 
 int clay_decode_device_strided(const clay_code_t *code, const uint8_t *chunks, int64_t node_stride,
                                int64_t stripe_stride, const size_t *er, size_t ner, uint8_t *out,
                                int64_t out_node_stride, int64_t out_stripe_stride, size_t ns, size_t chunk, int device,
                                void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    const DecStrided sd{chunks, node_stride, stripe_stride, out, out_node_stride, out_stripe_stride};
-    Error e = decode_batch_impl(code, nullptr, er, ner, nullptr, ns, chunk, device, stream, &sd);
-    return e ? report(e, err) : 0;
+    return abi_result(err, decode_batch_impl(code, StripeOperands::from_strides(chunks, node_stride, stripe_stride), er, ner,
+                                             StripeOperands::from_strides(out, out_node_stride, out_stripe_stride), ns,
+                                             chunk, device, stream));
 }
 
 int clay_decode_device_batch(const clay_code_t *code, const uint8_t *const *chunks, const size_t *er, size_t ner,
                              uint8_t *const *outs, size_t ns, size_t chunk, int device, void *stream,
                              clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = decode_batch_impl(code, chunks, er, ner, outs, ns, chunk, device, stream, nullptr);
-    return e ? report(e, err) : 0;
+    return abi_result(err, decode_batch_impl(code, StripeOperands::from_arrays(chunks), er, ner,
+                                             StripeOperands::from_arrays(outs), ns, chunk, device, stream));
 }
 
 int clay_repair_device(const clay_code_t *code, size_t lost, const size_t *ids, const uint8_t *const *bufs, size_t nh,
                        size_t chunk, uint8_t *out, int device, void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = repair_device_impl(code, lost, ids, bufs, nullptr, nh, chunk, out, device, stream);
-    return e ? report(e, err) : 0;
+    return abi_result(err, repair_device_impl(code, lost, ids, bufs, nullptr, nh, chunk, out, device, stream));
 }
 
 int clay_repair_device_full_chunks(const clay_code_t *code, size_t lost, const size_t *ids,
                                    const uint8_t *const *chunks, size_t nh, size_t chunk, uint8_t *out, int device,
                                    void *stream, clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = repair_device_impl(code, lost, ids, chunks, nullptr, nh, chunk, out, device, stream, true);
-    return e ? report(e, err) : 0;
+    return abi_result(err, repair_device_impl(code, lost, ids, chunks, nullptr, nh, chunk, out, device, stream, true));
 }
 
 int clay_repair_device_strided(const clay_code_t *code, size_t lost, const size_t *ids, size_t nh, const uint8_t *helpers,
                                int64_t node_stride, int64_t stripe_stride, int full_chunks, uint8_t *out,
                                int64_t out_stripe_stride, size_t ns, size_t chunk, int device, void *stream,
                                clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    const RepStrided sd{helpers, node_stride, stripe_stride, out, out_stripe_stride};
-    Error e = repair_batch_impl(code, lost, ids, nullptr, nh, full_chunks != 0, nullptr, ns, chunk, device, stream, &sd);
-    return e ? report(e, err) : 0;
+    return abi_result(err, repair_batch_impl(code, lost, ids, StripeOperands::from_strides(helpers, node_stride, stripe_stride),
+                                             nh, full_chunks != 0, StripeOperands::from_strides(out, 0, out_stripe_stride),
+                                             ns, chunk, device, stream));
 }
 
 int clay_repair_device_batch(const clay_code_t *code, size_t lost, const size_t *ids, const uint8_t *const *bufs, size_t nh,
                              int full_chunks, uint8_t *const *outs, size_t ns, size_t chunk, int device, void *stream,
                              clay_error_t *err) {
-    if (err) std::memset(err, 0, sizeof(*err));
-    Error e = repair_batch_impl(code, lost, ids, bufs, nh, full_chunks != 0, outs, ns, chunk, device, stream, nullptr);
-    return e ? report(e, err) : 0;
+    return abi_result(err, repair_batch_impl(code, lost, ids, StripeOperands::from_arrays(bufs), nh, full_chunks != 0,
+                                             StripeOperands::from_arrays(outs), ns, chunk, device, stream));
 }
 
 int clay_reserve_workspace(const clay_code_t *code, size_t chunk, int device, clay_error_t *err) {
@@ -3344,7 +3225,8 @@ int clay_encode_host_pipelined(const clay_code_t *code, const uint8_t *const *da
     e = host_pipeline(device, sc, ins, outs, piece_bytes, n_streams,
                       [&](const std::vector<const uint8_t *> &din, const std::vector<uint8_t *> &dout, size_t wp,
                           hipStream_t st) {
-                          return encode_device_impl(code, din.data(), dout.data(), 1, alpha * wp, device, st);
+                          return encode_device_impl(code, StripeOperands::from_arrays(din.data()),
+                                                    StripeOperands::from_arrays(dout.data()), 1, alpha * wp, device, st);
                       },
                       &launches);
     if (e) return report(e, err);
@@ -3394,7 +3276,8 @@ int clay_encode(const clay_code_t *code, const uint8_t *data, size_t len, uint8_
     e = host_pipeline(dev, sc, ins, outs, 0, 0,
                       [&](const std::vector<const uint8_t *> &din, const std::vector<uint8_t *> &dout, size_t wp,
                           hipStream_t st) {
-                          return encode_device_impl(code, din.data(), dout.data(), 1, alpha * wp, dev, st);
+                          return encode_device_impl(code, StripeOperands::from_arrays(din.data()),
+                                                    StripeOperands::from_arrays(dout.data()), 1, alpha * wp, dev, st);
                       },
                       &launches);
     copier.join();
