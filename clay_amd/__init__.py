@@ -122,7 +122,9 @@ def set_exec_mode(mode: str) -> str:
     'stream' (every decode a streaming kernel takes:
     local, else fused v2 from 2 erasures; the streaming repair kernel at any sub-chunk size),
     'stream-local' or 'stream-fused2' (that kernel wherever it applies).  Modes choose kernels
-    only: every mode returns the reference's bytes on any input.  Returns the previous mode."""
+    only: every mode returns the reference's bytes on any input.  The scrub of (4,2,5) runs the
+    line kernel ('bs-scrub1') except under 'grouped' / 'tile', which keep the v1 kernel
+    ('bs-scrub') for A/B; every other mode scrubs as auto.  Returns the previous mode."""
     if mode not in _EXEC_MODES:
         raise ValueError(f"unknown exec mode {mode!r}")
     prev = _lib.lib().clay_set_exec_mode(_EXEC_MODES[mode])
@@ -133,7 +135,8 @@ def last_exec_path() -> str:
     """Plan executor of this thread's last decode / repair / staged encode: 'tile' | 'grouped' |
     'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
     'bs-decode1-batch' (the batched decodes) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
-    (both) | 'none'."""
+    (both) | the scrubs' 'bs-scrub1' / 'bs-scrub' (one launch per stripe) and 'bs-scrub1-batch' /
+    'bs-scrub-batch' (a batch in one launch) | 'none'."""
     return _lib.lib().clay_last_exec_path().decode()
 
 
@@ -312,6 +315,71 @@ class ClayCode:
                                                    C.byref(err))
         if rc:
             _raise(rc, err)
+
+    # ---- scrub: do the stored chunks still form a codeword? ------------------
+    def scrub_device(self, data_chunks, parity_chunks, result, chunk_size: int, device: int = 0,
+                     stream: int = 0):
+        """Scrub one stripe in device memory (clay.h clay_scrub_device).  data_chunks: k device
+        buffers, parity_chunks: m, all read only; result: device memory of one uint32 (e.g. a
+        torch.int32 tensor), defined by the call: bit j set iff parity chunk j differs from the
+        encode of the data chunks.  A mismatch is a result, not an error.  Asynchronous on
+        `stream`.  Codes: (4,2,5), (6,3,8), (8,4,11), (9,3,11), (10,4,13)."""
+        dp = (C.c_void_p * self.k)(*[_ptr(x) for x in data_chunks])
+        pp = (C.c_void_p * self.m)(*[_ptr(x) for x in parity_chunks])
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_scrub_device(C.byref(self._c), dp, pp, int(chunk_size), C.c_void_p(_ptr(result)),
+                                          int(device), C.c_void_p(int(stream)), C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def scrub_device_batch(self, data_chunks, parity_chunks, result, n_stripes: int, chunk_size: int,
+                           device: int = 0, stream: int = 0):
+        """Scrub n_stripes stripes (clay.h clay_scrub_device_batch): stripe s uses
+        data_chunks[s*k .. s*k+k) and parity_chunks[s*m .. s*m+m); result: n_stripes uint32 in
+        device memory, one mask per stripe.  One launch where the stripes sit at uniform strides
+        (last_exec_path 'bs-scrub1-batch' / 'bs-scrub-batch'), else one per stripe."""
+        dp = (C.c_void_p * max(1, self.k * n_stripes))(*[_ptr(x) for x in data_chunks])
+        pp = (C.c_void_p * max(1, self.m * n_stripes))(*[_ptr(x) for x in parity_chunks])
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_scrub_device_batch(C.byref(self._c), dp, pp, C.c_void_p(_ptr(result)), int(n_stripes),
+                                                int(chunk_size), int(device), C.c_void_p(int(stream)),
+                                                C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def scrub_device_strided(self, data, parity, result, n_stripes: int, chunk_size: int,
+                             data_node_stride: int = 0, data_stripe_stride: int = 0, parity_node_stride: int = 0,
+                             parity_stripe_stride: int = 0, device: int = 0, stream: int = 0):
+        """Scrub stripes at fixed strides in one launch (clay.h clay_scrub_device_strided).
+        Strides default to a contiguous [n_stripes][k or m][chunk_size] layout; result:
+        n_stripes uint32 in device memory.  Allocates nothing: capturable unprepared."""
+        dns = data_node_stride or chunk_size
+        dss = data_stripe_stride or self.k * chunk_size
+        pns = parity_node_stride or chunk_size
+        pss = parity_stripe_stride or self.m * chunk_size
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_scrub_device_strided(C.byref(self._c), C.c_void_p(_ptr(data)), dns, dss,
+                                                  C.c_void_p(_ptr(parity)), pns, pss, C.c_void_p(_ptr(result)),
+                                                  int(n_stripes), int(chunk_size), int(device),
+                                                  C.c_void_p(int(stream)), C.byref(err))
+        if rc:
+            _raise(rc, err)
+
+    def verify(self, chunks) -> int:
+        """Host-buffer scrub (clay.h clay_verify, after reed-solomon-erasure's `verify`): chunks
+        = the n chunks of a stripe (bytes-likes of one size, k data then m parity).  Returns the
+        mismatch mask: 0 iff they form a codeword, bit j set iff parity chunk j differs from the
+        encode of the data chunks.  Blocks until the answer is in."""
+        arrs = [_np(c) for c in chunks]
+        if len(arrs) != self.n or any(a.size != arrs[0].size for a in arrs):
+            raise InconsistentChunkSizes(f"verify needs {self.n} chunks of one size")
+        ptrs = (C.POINTER(C.c_uint8) * self.n)(*[_u8(a) for a in arrs])
+        mask = C.c_uint32(0)
+        err = ClayErrorStruct()
+        rc = _lib.lib().clay_verify(C.byref(self._c), ptrs, arrs[0].size, C.byref(mask), C.byref(err))
+        if rc:
+            _raise(rc, err)
+        return int(mask.value)
 
     def chunk_to_ygroup(self, y: int, chunk, group, chunk_size: int, device: int = 0, stream: int = 0):
         """Reorder a device chunk into the y-grouped layout of y-section y (clay.h)."""

@@ -69,6 +69,11 @@ SIGNATURES = {
     "clay_ygroup_to_chunk": (C.c_int, [_code_p, _sz, C.c_void_p, C.c_void_p, _sz, C.c_int, C.c_void_p, _err_p]),
     "clay_encode_device_strided": (C.c_int, [_code_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_int64, _sz, _sz, C.c_int, C.c_void_p, _err_p]),
+    "clay_scrub_device": (C.c_int, [_code_p, _P(_vp), _P(_vp), _sz, C.c_void_p, C.c_int, _vp, _err_p]),
+    "clay_scrub_device_batch": (C.c_int, [_code_p, _P(_vp), _P(_vp), C.c_void_p, _sz, _sz, C.c_int, _vp, _err_p]),
+    "clay_scrub_device_strided": (C.c_int, [_code_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_int64, C.c_void_p, _sz, _sz, C.c_int, C.c_void_p, _err_p]),
+    "clay_verify": (C.c_int, [_code_p, _P(_u8p), _sz, _P(C.c_uint32), _err_p]),
     "clay_workspace_bytes": (_sz, [C.c_int]),
     "clay_plan_export": (C.c_int, [_code_p, C.c_int, _u8p, _u8p, _sz, _P(C.c_uint32), _sz,
                                    _P(C.c_uint32), _sz, _P(C.c_uint32), _sz, _P(_sz), _err_p]),

@@ -228,6 +228,9 @@ struct BsArgs {
     // (ntiles tiles per stripe, tiles_per_xcd over all nstripes * ntiles); 0 = one stripe
     uint32_t nstripes;
     int64_t sdata, spar;
+    // SCRUB instantiations: result word of stripe 0 (stripe s ORs its mismatch bits into res[s]);
+    // ntiles = 0 is their clear mode: res[0 .. sc) = 0 and nothing else.  The encodes ignore it
+    uint32_t *res;
 };
 
 // Code shape derived at compile time from (k, m) with d = k + m - 1 (q = m).
@@ -285,6 +288,46 @@ __device__ __forceinline__ void st32(uint8_t *p, const uint32_t (&d)[8], int nv)
             for (int b = 8 * i; b < nv; b++) p[b] = uint8_t(d[2 * i + ((b >> 2) & 1)] >> (8 * (b & 3)));
         }
     }
+}
+
+// SCRUB ending (what a compare-ending kernel does where the encode has its st32): the stored
+// 32 bytes at p against d.  Returns the OR of stored ^ d over the lane's valid positions (nv as
+// in ld32 / st32): 0 iff they are equal.  In a partial tile ld32 zero-fills what lies at or past
+// sc, and d there is the image of zero-filled loads under a linear map, so both sides are 0; the
+// mask below does not lean on either: a word takes part only with its bytes below nv.
+template <bool FULL, bool BT = false>
+__device__ __forceinline__ uint32_t cmp32(const uint8_t *p, const uint32_t (&d)[8], int nv) {
+    uint32_t s[8], r = 0;
+    ld32<FULL, BT>(s, p, nv);
+    const int nb = BT ? nv : 8 * nv;  // valid bytes
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        uint32_t x = s[w] ^ d[w];
+        if constexpr (!FULL) {
+            const int vb = nb - 4 * w;
+            x &= vb >= 4 ? 0xffffffffu : vb <= 0 ? 0u : (1u << (8 * vb)) - 1u;
+        }
+        r |= x;
+    }
+    return r;
+}
+// SCRUB: OR the lanes' mismatch bits (bit x = parity node x) over the wave; a wave that saw a
+// mismatch issues one device-scope atomic OR into its stripe's result word, a clean wave none.
+// Called in workgroup-uniform control flow (blocks are one-dimensional: lane = threadIdx.x % 64).
+template <int M>
+__device__ __forceinline__ void scrub_report(uint32_t *res, uint32_t bits) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int x = 0; x < M; x++) any |= __ballot(int((bits >> x) & 1u)) ? 1u << x : 0u;
+    if (any && (threadIdx.x & 63u) == 0) atomicOr(res, any);
+}
+
+// SCRUB, clear mode (ntiles = 0, sc = the word count): the launch that defines the result words
+// ahead of the compare launch on the same stream.  A kernel node where a memset would do: a
+// captured hipMemsetAsync has been seen to replay a stale fill value.
+__device__ __forceinline__ void scrub_clear(uint32_t *res, uint64_t n) {
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x)
+        res[i] = 0;
 }
 
 template <int KD, int M, int PG>
@@ -377,8 +420,11 @@ struct BsKernel {
     }
 
     // ---- phase B: PFT of the parity y-section (digit t-1, weight 1) + store ----
-    template <bool FULL, bool BT>
-    __device__ static void finish(const BsArgs &a, const uint32_t *lds, uint64_t b0, int64_t poff) {
+    // SCRUB: the stores become compares against the stored parity (cmp32) and nothing is written;
+    // the mismatch bits go to a.res[stripe] (the tile's stripe is workgroup-uniform)
+    template <bool FULL, bool BT, bool SCRUB = false>
+    __device__ static void finish(const BsArgs &a, const uint32_t *lds, uint64_t b0, int64_t poff, uint32_t stripe = 0) {
+        uint32_t bad = 0;  // SCRUB: bit x = parity node x differs somewhere in this lane's positions
         for (int u = threadIdx.x; u < UNITS; u += BLOCK) {
             const int pg = u % PG, j = (u / PG) % Q, g = u / (PG * Q);
             const int z0 = g * Q;
@@ -391,7 +437,8 @@ struct BsKernel {
                 uint32_t v[8];
                 read8(lds, j, z0 + j, pg, v);
                 transpose8(v);
-                st32<FULL, BT>(a.par[j] + poff + off, v, nv);
+                if constexpr (SCRUB) bad |= cmp32<FULL, BT>(a.par[j] + poff + off, v, nv) ? 1u << j : 0u;
+                else st32<FULL, BT>(a.par[j] + poff + off, v, nv);
             }
 #pragma unroll
             for (int k = 1; k < Q; k++) {
@@ -403,25 +450,32 @@ struct BsKernel {
                     c[decltype(bc)::value] = xor_sel<pft_mask<decltype(bc)::value>(), false>(0u, in);
                 });
                 transpose8(c);
-                st32<FULL, BT>(a.par[x] + poff + off, c, nv);
+                if constexpr (SCRUB) bad |= cmp32<FULL, BT>(a.par[x] + poff + off, c, nv) ? 1u << x : 0u;
+                else st32<FULL, BT>(a.par[x] + poff + off, c, nv);
             }
         }
+        if constexpr (SCRUB) scrub_report<M>(a.res + stripe, bad);
     }
 
-    template <bool FULL, bool BT>
-    __device__ static void tile(const BsArgs &a, uint32_t *lds, uint64_t b0, int64_t doff = 0, int64_t poff = 0) {
+    template <bool FULL, bool BT, bool SCRUB = false>
+    __device__ static void tile(const BsArgs &a, uint32_t *lds, uint64_t b0, int64_t doff = 0, int64_t poff = 0,
+                                uint32_t stripe = 0) {
         sfor<T - 1>([&](auto yc) BS_INL {
             section<decltype(yc)::value, FULL, BT>(a, lds, b0, doff);
             __syncthreads();
         });
-        finish<FULL, BT>(a, lds, b0, poff);
+        finish<FULL, BT, SCRUB>(a, lds, b0, poff, stripe);
         __syncthreads();
     }
 };
 
-template <int KD, int M, int PG, bool BT = false>
+// SCRUB: the compare-ending variant (finish): reads the stored parity, writes a.res only
+template <int KD, int M, int PG, bool BT = false, bool SCRUB = false>
 __global__ __launch_bounds__((BsKernel<KD, M, PG>::BLOCK)) void k_bs_encode(BsArgs a) {
     using Kn = BsKernel<KD, M, PG>;
+    if constexpr (SCRUB) {
+        if (a.ntiles == 0) return scrub_clear(a.res, a.sc);  // the clear launch ahead of the compare
+    }
     __shared__ __attribute__((aligned(16))) uint32_t lds[Kn::LDS_WORDS];
     const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
     const uint32_t ns = a.nstripes ? a.nstripes : 1u, total = a.ntiles * ns;
@@ -432,8 +486,8 @@ __global__ __launch_bounds__((BsKernel<KD, M, PG>::BLOCK)) void k_bs_encode(BsAr
         const uint32_t stripe = ft / a.ntiles, tile = ft - stripe * a.ntiles;
         const uint64_t b0 = uint64_t(tile) * Kn::W;
         const int64_t doff = int64_t(stripe) * a.sdata, poff = int64_t(stripe) * a.spar;
-        if (b0 + Kn::W <= a.sc) Kn::template tile<true, BT>(a, lds, b0, doff, poff);
-        else Kn::template tile<false, BT>(a, lds, b0, doff, poff);
+        if (b0 + Kn::W <= a.sc) Kn::template tile<true, BT, SCRUB>(a, lds, b0, doff, poff, stripe);
+        else Kn::template tile<false, BT, SCRUB>(a, lds, b0, doff, poff, stripe);
     }
 }
 

@@ -271,8 +271,11 @@ struct Enc1Kernel {
         }
     }
 
-    template <bool FULL, bool BT>
-    __device__ static void tile(const Enc1Args &a, uint64_t b0, int64_t doff, int64_t poff) {
+    // SCRUB: the stores become compares against the stored parity (bitslice.hpp cmp32), nothing
+    // is written; the mismatch bits go to a.res[stripe] (the tile's stripe is workgroup-uniform)
+    template <bool FULL, bool BT, bool SCRUB = false>
+    __device__ static void tile(const Enc1Args &a, uint64_t b0, int64_t doff, int64_t poff, uint32_t stripe = 0) {
+        uint32_t bad = 0;  // SCRUB: bit x = parity node x differs somewhere in this lane's positions
         for (int u = threadIdx.x; u < UNITS; u += BLOCK) {
             const int pg = u % PG, line = u / PG;
             const uint32_t z0 = uint32_t(line * Q);
@@ -333,16 +336,23 @@ struct Enc1Kernel {
                         });
                     }
                     transpose8(c);
-                    st32<FULL, BT>(a.par[x] + poff + uint64_t(z0 + uint32_t(j)) * a.sc + pos, c, nv);
+                    uint8_t *dst = a.par[x] + poff + uint64_t(z0 + uint32_t(j)) * a.sc + pos;
+                    if constexpr (SCRUB) bad |= cmp32<FULL, BT>(dst, c, nv) ? 1u << x : 0u;
+                    else st32<FULL, BT>(dst, c, nv);
                 });
             });
         }
+        if constexpr (SCRUB) scrub_report<M>(a.res + stripe, bad);
     }
 };
 
-template <int KD, int M, int PG, bool BT = false>
+// SCRUB: the compare-ending variant (tile): reads the stored parity, writes a.res only
+template <int KD, int M, int PG, bool BT = false, bool SCRUB = false>
 __global__ __launch_bounds__((Enc1Kernel<KD, M, PG>::BLOCK)) void k_bs_encode1(Enc1Args a) {
     using Kn = Enc1Kernel<KD, M, PG>;
+    if constexpr (SCRUB) {
+        if (a.ntiles == 0) return scrub_clear(a.res, a.sc);  // the clear launch ahead of the compare
+    }
     const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
     const uint32_t ns = a.nstripes ? a.nstripes : 1u, total = a.ntiles * ns;
     for (uint32_t tix = slot; tix < a.tiles_per_xcd; tix += a.nslots) {
@@ -352,8 +362,8 @@ __global__ __launch_bounds__((Enc1Kernel<KD, M, PG>::BLOCK)) void k_bs_encode1(E
         const uint32_t stripe = ft / a.ntiles, tile = ft - stripe * a.ntiles;
         const uint64_t b0 = uint64_t(tile) * Kn::W;
         const int64_t doff = int64_t(stripe) * a.sdata, poff = int64_t(stripe) * a.spar;
-        if (b0 + Kn::W <= a.sc) Kn::template tile<true, BT>(a, b0, doff, poff);
-        else Kn::template tile<false, BT>(a, b0, doff, poff);
+        if (b0 + Kn::W <= a.sc) Kn::template tile<true, BT, SCRUB>(a, b0, doff, poff, stripe);
+        else Kn::template tile<false, BT, SCRUB>(a, b0, doff, poff, stripe);
     }
 }
 

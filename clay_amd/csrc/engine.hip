@@ -37,6 +37,7 @@
 #include "repair_batch_map.hpp"  // its batch form's column map
 #include "decode_args.hpp"  // streaming-decode kernel: stream_decode.hpp, instantiated in decode_stream.hip
 #include "line_args.hpp"  // line-local bit-sliced (4,2,5) encode / single-erasure decode: bitslice_line.hpp, in line_kernels.hip
+#include "scrub_args.hpp"  // compare-ending instantiations of the two bit-sliced encodes, in scrub_kernels.hip
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "tuning.hpp"
@@ -1866,6 +1867,173 @@ static Error encode_device_impl(const clay_code_t *code, StripeOperands data, St
 }
 
 // ---------------------------------------------------------------------------
+// Scrub: do the stored parity chunks match the encode of the stored data chunks?  The
+// compare-ending (SCRUB) instantiations of the two bit-sliced encode kernels (scrub_kernels.hip):
+// no scratch memory, no pointer table, nothing written but the result words.
+// ---------------------------------------------------------------------------
+constexpr char kScrubCodes[] = "Invalid parameters: scrub has kernels for (4,2,5), (6,3,8), (8,4,11), (9,3,11) and (10,4,13) only";
+static bool scrub_code_ok(const clay_code_t &c) {
+    const int key = int(c.k * 100 + c.m);
+    return c.d == c.k + c.m - 1 && (key == 402 || key == 603 || key == 804 || key == 903 || key == 1004);
+}
+
+// ns stripes at stripe 0's pointers + s * sdata / spar, one launch (ns == 1: one stripe).
+// *done = false: more (stripe, tile) pairs than the kernel's 32-bit flattening holds.
+static Error launch_bs_scrub1(CodeState &cs, const DevProps &prop, uint8_t *const *data0, uint8_t *const *par0,
+                              int64_t sdata, int64_t spar, size_t ns, size_t sc, uint32_t *res, hipStream_t stream,
+                              bool *done) {
+    *done = false;
+    using Kn = bs::BsKernel<4, 2, ScrubPg<4, 2>::value>;  // the line kernel's tile is v1's
+    if (Error e = rs_matches<bs::Shape<4, 2>, 2>(cs)) return e;
+    const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
+    if (ntiles * ns >= 0xFFFFFFFFull) return Error{};
+    bs::Enc1Args a{};
+    for (int i = 0; i < 4; i++) a.data[i] = data0[i];
+    for (int x = 0; x < 2; x++) a.par[x] = par0[x];
+    a.sc = sc;
+    a.ntiles = uint32_t(ntiles);
+    a.nstripes = uint32_t(ns);
+    a.sdata = sdata;
+    a.spar = spar;
+    a.res = res;
+    line_slots(a, ntiles * ns, prop);
+    const bool bt = sc % 8 != 0 || misaligned8(a.data, 4, sdata) || misaligned8(a.par, 2, spar);
+    CLAY_HIP(launch_bs_scrub1_kernel(4, 2, bt, a, stream));
+    t_last_launches++;
+    *done = true;
+    return Error{};
+}
+
+template <int KD, int M>
+static Error launch_bs_scrub(CodeState &cs, const DevProps &prop, uint8_t *const *data0, uint8_t *const *par0,
+                             int64_t sdata, int64_t spar, size_t ns, size_t sc, uint32_t *res, hipStream_t stream,
+                             bool *done) {
+    *done = false;
+    using Kn = bs::BsKernel<KD, M, ScrubPg<KD, M>::value>;
+    using S = typename Kn::S;
+    if (Error e = rs_matches<S, M>(cs)) return e;
+    const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
+    if (ntiles * ns >= 0xFFFFFFFFull) return Error{};
+    const int per_cu = std::max(1, int((160 * 1024) / (Kn::LDS_WORDS * 4)));
+    bs::BsArgs a{};
+    for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? data0[i] : nullptr;
+    for (int x = 0; x < M; x++) a.par[x] = par0[x];
+    a.sc = sc;
+    a.ntiles = uint32_t(ntiles);
+    a.nstripes = uint32_t(ns);
+    a.sdata = sdata;
+    a.spar = spar;
+    a.res = res;
+    a.tiles_per_xcd = uint32_t((ntiles * ns + 7) / 8);
+    a.nslots = std::min(uint32_t(std::max(1, prop.raw.multiProcessorCount / 8) * per_cu), a.tiles_per_xcd);
+    const bool bt = sc % 8 != 0 || misaligned8(a.data, KD, sdata) || misaligned8(a.par, M, spar);  // byte tails
+    CLAY_HIP(launch_bs_scrub_kernel(KD, M, bt, a, stream));
+    t_last_launches++;
+    *done = true;
+    return Error{};
+}
+
+// data / par: as encode_device_impl's, both read-only here.  result: n_stripes device words, every
+// one defined by the call (cleared on `stream` by the kernel's clear mode, then bit j of result[s] set iff
+// parity chunk j of stripe s differs from the encode of the stripe's data chunks).  batch_call:
+// the batch / strided entry points (they name the "-batch" paths, for one stripe too).
+static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, StripeOperands par, uint32_t *result,
+                               size_t n_stripes, size_t chunk, int dev, void *stream, bool batch_call) {
+    Error e = check_code(code);
+    if (e) return e;
+    const clay_code_t &c = *code;
+    data.per = c.k;
+    par.per = c.m;
+    if (data.null() || par.null())
+        return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
+    if (chunk == 0 || chunk % c.sub_chunk_no != 0)
+        return make_error(CLAY_ERR_INVALID_CHUNK_SIZE, c.sub_chunk_no, chunk, 0,
+                          "Invalid chunk size: expected divisible by %zu, got %zu", c.sub_chunk_no, chunk);
+    if (!data.strided) {
+        for (size_t i = 0; i < n_stripes * c.k; i++)
+            if (!data.ptrs[i]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null data chunk");
+        for (size_t i = 0; i < n_stripes * c.m; i++)
+            if (!par.ptrs[i]) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null parity chunk");
+    }
+    if (n_stripes > 0 && !result)
+        return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null scrub result");
+    if (!scrub_code_ok(c)) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, kScrubCodes);
+    if (n_stripes == 0) return Error{};
+    t_last_launches = 0;
+    Opened o;
+    e = o.open(c, dev);
+    if (e) return e;
+    CodeState &cs = *o.cs;
+    if (cs.rs.init_err)
+        return make_error(CLAY_ERR_RECONSTRUCTION_FAILED, 0, 0, 0, "RS reconstruction failed: RS init failed: %s",
+                          rs_error_name(cs.rs.init_err));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DevProps &prop = dev_props(dev);
+    const size_t sc = chunk / c.sub_chunk_no;
+    const int key = int(c.k * 100 + c.m);
+    const int xm = g_exec_mode.load(std::memory_order_relaxed);
+    // (4,2,5): the line kernel; "grouped" / "tile" keep v1, its A/B partner
+    const bool line = key == 402 && xm != kExecGrouped && xm != kExecTile;
+    auto launch = [&](uint8_t *const *d0, uint8_t *const *p0, int64_t sdata, int64_t spar, size_t ns, uint32_t *res,
+                      bool *done) {
+        if (line) return launch_bs_scrub1(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
+        switch (key) {
+        case 402: return launch_bs_scrub<4, 2>(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
+        case 603: return launch_bs_scrub<6, 3>(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
+        case 804: return launch_bs_scrub<8, 4>(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
+        case 903: return launch_bs_scrub<9, 3>(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
+        default: return launch_bs_scrub<10, 4>(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
+        }
+    };
+    // result[0 .. n_stripes) = 0 on the caller's stream: the picked kernel's clear mode (ntiles = 0,
+    // sc = the word count).  A kernel where hipMemsetAsync would do, because a captured memset
+    // node has been seen to replay a stale fill value; like a memset it is not
+    // counted in clay_last_launch_count.
+    {
+        const uint32_t slots = uint32_t(std::min<size_t>(128, (n_stripes + 2047) / 2048));
+        if (line) {
+            bs::Enc1Args a{};
+            a.res = result;
+            a.sc = n_stripes;
+            a.nslots = slots;
+            CLAY_HIP(launch_bs_scrub1_kernel(4, 2, false, a, st));
+        } else {
+            bs::BsArgs a{};
+            a.res = result;
+            a.sc = n_stripes;
+            a.nslots = slots;
+            CLAY_HIP(launch_bs_scrub_kernel(int(c.k), int(c.m), false, a, st));
+        }
+    }
+    std::vector<uint8_t *> d0(c.k), p0(c.m);
+    // stripes at one data and one parity stride: one launch, at any sub-chunk size (there is no
+    // staged alternative that would pack small sub-chunks better)
+    int64_t sdata = 0, spar = 0;
+    if (batch_call && uniform_stride(data, 0, n_stripes, nullptr, c.k, &sdata) &&
+        uniform_stride(par, 0, n_stripes, nullptr, c.m, &spar)) {
+        data.stripe_ptrs(0, d0.data());
+        par.stripe_ptrs(0, p0.data());
+        bool done = false;
+        e = launch(d0.data(), p0.data(), sdata, spar, n_stripes, result, &done);
+        if (e) return e;
+        if (done) {
+            t_last_exec = line ? "bs-scrub1-batch" : "bs-scrub-batch";
+            return Error{};
+        }
+    }
+    for (size_t s = 0; s < n_stripes; s++) {
+        data.stripe_ptrs(s, d0.data());
+        par.stripe_ptrs(s, p0.data());
+        bool done = false;
+        e = launch(d0.data(), p0.data(), 0, 0, 1, result + s, &done);
+        if (e) return e;
+        if (!done) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "scrub: chunk too large for the kernel's tile count");
+    }
+    t_last_exec = line ? "bs-scrub1" : "bs-scrub";
+    return Error{};
+}
+
+// ---------------------------------------------------------------------------
 // Decode / repair on device
 // ---------------------------------------------------------------------------
 // The streaming decodes (stream_decode.hpp phase A + stream_local.hpp / stream_fused2.hpp) for
@@ -2955,6 +3123,94 @@ int clay_encode_device_strided(const clay_code_t *code, const uint8_t *data, int
     return abi_result(err, encode_device_impl(code, StripeOperands::from_strides(data, data_node_stride, data_stripe_stride),
                                               StripeOperands::from_strides(parity, parity_node_stride, parity_stripe_stride),
                                               n_stripes, chunk, device, stream));
+}
+
+int clay_scrub_device(const clay_code_t *code, const uint8_t *const *data, const uint8_t *const *par, size_t chunk,
+                      uint32_t *result, int device, void *stream, clay_error_t *err) {
+    return abi_result(err, scrub_device_impl(code, StripeOperands::from_arrays(data), StripeOperands::from_arrays(par),
+                                             result, 1, chunk, device, stream, false));
+}
+
+int clay_scrub_device_batch(const clay_code_t *code, const uint8_t *const *data, const uint8_t *const *par,
+                            uint32_t *result, size_t ns, size_t chunk, int device, void *stream, clay_error_t *err) {
+    return abi_result(err, scrub_device_impl(code, StripeOperands::from_arrays(data), StripeOperands::from_arrays(par),
+                                             result, ns, chunk, device, stream, true));
+}
+
+int clay_scrub_device_strided(const clay_code_t *code, const uint8_t *data, int64_t data_node_stride,
+                              int64_t data_stripe_stride, const uint8_t *parity, int64_t parity_node_stride,
+                              int64_t parity_stripe_stride, uint32_t *result, size_t ns, size_t chunk, int device,
+                              void *stream, clay_error_t *err) {
+    return abi_result(err, scrub_device_impl(code, StripeOperands::from_strides(data, data_node_stride, data_stripe_stride),
+                                             StripeOperands::from_strides(parity, parity_node_stride, parity_stripe_stride),
+                                             result, ns, chunk, device, stream, true));
+}
+
+// The host-buffer scrub: the n chunks into one pooled device buffer (rows padded to 8 bytes, the
+// result word behind them), one scrub call, the mask back; blocks until its own work is done.
+static Error verify_impl(const clay_code_t *code, const uint8_t *const *chunks, size_t chunk, uint32_t *mask_out) {
+    Error e = check_code(code);
+    if (e) return e;
+    const clay_code_t &c = *code;
+    if (!chunks || !mask_out)
+        return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, "Invalid parameters: null chunk array");
+    if (chunk == 0 || chunk % c.sub_chunk_no != 0)
+        return make_error(CLAY_ERR_INVALID_CHUNK_SIZE, c.sub_chunk_no, chunk, 0,
+                          "Invalid chunk size: expected divisible by %zu, got %zu", c.sub_chunk_no, chunk);
+    for (size_t i = 0; i < c.n; i++)
+        if (!chunks[i])
+            return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0,
+                              i < c.k ? "Invalid parameters: null data chunk" : "Invalid parameters: null parity chunk");
+    if (!scrub_code_ok(c)) return make_error(CLAY_ERR_INVALID_PARAMETERS, 0, 0, 0, kScrubCodes);
+    const int dev = current_device(&e);
+    if (e) return e;
+    DevState *ds;
+    e = dev_state(dev, &ds);
+    if (e) return e;
+    DeviceGuard g(dev);
+    // a stream and a buffer from the device's pools, handed back on every exit path once the
+    // stream has drained (copies from the caller's buffers may still be queued on an error)
+    struct Res {
+        DevState &ds;
+        hipStream_t st = nullptr;
+        Lease *buf = nullptr;
+        ~Res() {
+            if (!st) return;
+            (void)hipStreamSynchronize(st);
+            lease_release(ds, buf, st);
+            std::lock_guard<std::mutex> lk(ds.mu);
+            ds.host_streams.push_back(st);
+        }
+    } r{*ds};
+    {
+        std::lock_guard<std::mutex> lk(ds->mu);
+        if (!ds->host_streams.empty()) {
+            r.st = ds->host_streams.back();
+            ds->host_streams.pop_back();
+        }
+    }
+    if (!r.st) CLAY_HIP(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
+    const size_t pitch = (chunk + 7) / 8 * 8;
+    e = lease_acquire(*ds, c.n * pitch + 8, r.st, &r.buf);
+    if (e) return e;
+    uint8_t *buf = static_cast<uint8_t *>(r.buf->d);
+    uint32_t *res = reinterpret_cast<uint32_t *>(buf + c.n * pitch);
+    for (size_t i = 0; i < c.n; i++)
+        CLAY_HIP(hipMemcpyAsync(buf + i * pitch, chunks[i], chunk, hipMemcpyHostToDevice, r.st));
+    e = scrub_device_impl(code, StripeOperands::from_strides(buf, int64_t(pitch), 0),
+                          StripeOperands::from_strides(buf + c.k * pitch, int64_t(pitch), 0), res, 1, chunk, dev, r.st,
+                          false);
+    if (e) return e;
+    uint32_t mask = 0;
+    CLAY_HIP(hipMemcpyAsync(&mask, res, 4, hipMemcpyDeviceToHost, r.st));
+    CLAY_HIP(hipStreamSynchronize(r.st));
+    *mask_out = mask;
+    return Error{};
+}
+
+int clay_verify(const clay_code_t *code, const uint8_t *const *chunks, size_t chunk, uint32_t *mask_out,
+                clay_error_t *err) {
+    return abi_result(err, verify_impl(code, chunks, chunk, mask_out));
 }
 
 static Error ygroup_impl(const clay_code_t *code, size_t y, const uint8_t *src, uint8_t *dst, size_t chunk, int dev,

@@ -30,6 +30,9 @@ struct Enc1Args {
     // stripe, tiles_per_xcd over all nstripes * ntiles); nstripes = 0: one stripe
     uint32_t nstripes;
     int64_t sdata, spar;
+    // SCRUB instantiations: result word of stripe 0 (stripe s ORs its mismatch bits into res[s]);
+    // ntiles = 0 is their clear mode: res[0 .. sc) = 0 and nothing else.  The encode ignores it
+    uint32_t *res;
 };
 
 }  // namespace bs

@@ -1,0 +1,28 @@
+// scrub_args.hpp -- launchers of the compare-ending (SCRUB) instantiations of the two bit-sliced
+// encode kernels, shared by the host (engine.hip) and their translation unit (scrub_kernels.hip).
+// The kernels take the encodes' argument structs (Enc1Args of line_args.hpp, BsArgs of
+// bitslice.hpp) with `res` set: they read data and stored parity, write nothing but res[stripe].
+#pragma once
+#include "bitslice.hpp"
+#include "line_args.hpp"
+
+namespace clay {
+
+// scrub_kernels.hip: k_bs_encode1<.., SCRUB> for code (k, m), grid a.nslots * 8; bt = byte tails.
+// hipErrorInvalidValue: no instantiation
+hipError_t launch_bs_scrub1_kernel(int k, int m, bool bt, const bs::Enc1Args &a, hipStream_t stream);
+// scrub_kernels.hip: k_bs_encode<.., SCRUB> (v1) for code (k, m) with d = k + m - 1, grid
+// a.nslots * 8; bt = byte tails.  hipErrorInvalidValue: no instantiation
+hipError_t launch_bs_scrub_kernel(int k, int m, bool bt, const bs::BsArgs &a, hipStream_t stream);
+
+// The one column-group count (PG) per code the v1 scrub is instantiated with: the host sizes
+// tiles and slots from BsKernel<KD, M, ScrubPg<KD, M>::value>
+template <int KD, int M>
+struct ScrubPg;
+template <> struct ScrubPg<4, 2> { static constexpr int value = 64; };
+template <> struct ScrubPg<6, 3> { static constexpr int value = 16; };
+template <> struct ScrubPg<8, 4> { static constexpr int value = 8; };
+template <> struct ScrubPg<9, 3> { static constexpr int value = 6; };
+template <> struct ScrubPg<10, 4> { static constexpr int value = 2; };
+
+}  // namespace clay

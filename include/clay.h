@@ -169,6 +169,57 @@ int clay_encode_device_strided(const clay_code_t *code, const uint8_t *data, int
                                int64_t parity_stripe_stride, size_t n_stripes, size_t chunk_size, int device,
                                void *stream, clay_error_t *err);
 
+/* Scrub: do the stored chunks of a stripe still form a codeword?  (reed-solomon-erasure,
+ * the crate under the reference, ships `verify`; the reference's Clay layer has no
+ * counterpart.)  data_chunks: k device pointers, parity_chunks: m device pointers
+ * (chunk_size bytes each), all read only: nothing is ever written to them.  result:
+ * device memory of one uint32_t, defined by the call (the caller need not clear it): bit j
+ * is set iff parity chunk j (node k + j) differs, at any byte, from the parity
+ * clay_encode_device gives for the data chunks.  A mismatch is a result, not an error: the
+ * call returns CLAY_OK.  Asynchronous on `stream`: the clear of `result`, then one launch of
+ * the compare-ending variant of the bit-sliced encode, which loads the stored parity where
+ * the encode stores it.  (The clear is a small launch of the same kernel in its clear mode,
+ * not a hipMemsetAsync -- a captured memset node has been seen to replay a stale fill value --
+ * and like a memset it is not counted in clay_last_launch_count.)  No scratch memory, no
+ * allocation, so the call may be captured unprepared.
+ * Any sub-chunk size and alignment.  Codes: (4,2,5), (6,3,8), (8,4,11), (9,3,11) and
+ * (10,4,13); any other code is CLAY_ERR_INVALID_PARAMETERS.  Validation is
+ * clay_encode_device's; a NULL result is CLAY_ERR_INVALID_PARAMETERS.  Last exec path
+ * "bs-scrub1" ((4,2,5); k_bs_encode1) or "bs-scrub" (k_bs_encode; (4,2,5) under exec modes
+ * 1 / 2).  clay_set_encode_path has no effect. */
+int clay_scrub_device(const clay_code_t *code, const uint8_t *const *data_chunks,
+                      const uint8_t *const *parity_chunks, size_t chunk_size, uint32_t *result,
+                      int device, void *stream, clay_error_t *err);
+
+/* Batched scrub: `n_stripes` independent stripes, stripe s uses data_chunks[s*k .. s*k+k)
+ * and parity_chunks[s*m .. s*m+m); result: n_stripes uint32_t in device memory, result[s]
+ * the mask of stripe s, every word defined by the call.  Stripes that sit at one data and
+ * one parity stride (rows of one buffer) run in ONE launch at any sub-chunk size (last exec
+ * path "bs-scrub1-batch" / "bs-scrub-batch"); any other arrangement takes one launch per
+ * stripe ("bs-scrub1" / "bs-scrub", clay_last_launch_count = n_stripes).  n_stripes = 0
+ * returns CLAY_OK and touches nothing. */
+int clay_scrub_device_batch(const clay_code_t *code, const uint8_t *const *data_chunks,
+                            const uint8_t *const *parity_chunks, uint32_t *result, size_t n_stripes,
+                            size_t chunk_size, int device, void *stream, clay_error_t *err);
+
+/* Batched scrub of stripes at fixed strides, the layout of clay_encode_device_strided: data
+ * node i of stripe s at data + s*data_stripe_stride + i*data_node_stride, parity node j at
+ * parity + s*parity_stripe_stride + j*parity_node_stride.  Always one launch, O(1) host
+ * work.  Bytes between the chunks are never read into the answer. */
+int clay_scrub_device_strided(const clay_code_t *code, const uint8_t *data, int64_t data_node_stride,
+                              int64_t data_stripe_stride, const uint8_t *parity, int64_t parity_node_stride,
+                              int64_t parity_stripe_stride, uint32_t *result, size_t n_stripes,
+                              size_t chunk_size, int device, void *stream, clay_error_t *err);
+
+/* Host-buffer scrub, in the spirit of reed-solomon-erasure's `verify`: chunks = the n host
+ * chunks of a stripe (k data, then m parity; chunk_size bytes each, chunk_size %
+ * sub_chunk_no == 0).  Copies them to the current device (one pooled buffer), scrubs, and
+ * returns the mask of clay_scrub_device in *mask_out (host memory) once its own work is
+ * done; 0 = a codeword.  Validates as clay_encode_host_pipelined; same codes as
+ * clay_scrub_device. */
+int clay_verify(const clay_code_t *code, const uint8_t *const *chunks, size_t chunk_size,
+                uint32_t *mask_out, clay_error_t *err);
+
 /* Y-grouped chunk layout ("Option C" of the reference's
  * docs/clay-practical-implementation.md:416-582, in the crate's MSB-first digit order):
  * for y-section y, the chunk's alpha sub-chunks reordered as blocks x = 0..q-1 of beta
@@ -395,6 +446,9 @@ int clay_set_encode_path(int mode);
  *    the bit-sliced repair kernels: k_bs_repair_stream (LDS-DMA streaming, one workgroup per
  *    CU; auto when the sub-chunk gives every CU a tile, stream for any sub-chunk >= 16 bytes
  *    of (9,3,11) / (10,4,13); last path "bs-repair-stream"), else k_bs_repair ("bs-repair"))
+ *   (scrubs, clay_scrub_device*: (4,2,5) on the line kernel, "bs-scrub1" / "bs-scrub1-batch",
+ *    except under 1 grouped and 2 tile, which keep v1, "bs-scrub" / "bs-scrub-batch", its A/B
+ *    partner; every other code on v1 in every mode)
  *   3 stream  -- every decode a streaming kernel takes on it: the local decode where it takes
  *                the pattern (the (2,1) patterns: the fused decode v2 first), else the fused
  *                decode v2 (2-4 erasures, at most two per section); everything else as auto
@@ -418,7 +472,9 @@ int clay_set_exec_mode(int mode);
  * (k_stream_fused2), "bs-decode1" (k_bs_decode1), "bs-repair-stream" (k_bs_repair_stream),
  * "bs-repair" (k_bs_repair), the batched decodes' "bs-decode1-batch" (k_bs_decode1 over many
  * stripes), the batched repairs' "bs-repair-batch" (k_bs_repair over many stripes), both batches'
- * "grouped-batch" (k_gexec over many stripes), or "none". */
+ * "grouped-batch" (k_gexec over many stripes), the scrubs' "bs-scrub1" (k_bs_encode1's compare
+ * ending) / "bs-scrub" (k_bs_encode's) with one launch per stripe and "bs-scrub1-batch" /
+ * "bs-scrub-batch" (a batch in one launch), or "none". */
 const char *clay_last_exec_path(void);
 
 /* Name of the path the last encode on this thread used ("fused-q4w128p8", "staged", ...). */

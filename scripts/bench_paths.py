@@ -4,6 +4,7 @@ HBM, HIP events on the launch stream, median of N runs).  Algorithmic bytes per 
 encode  read k*chunk + write m*chunk
 decode  read (n-e)*chunk + write (#erased data nodes)*chunk
 repair  read d*beta*sc + write chunk
+scrub   read n*chunk (ONLY=scrub)
 Prints one JSON object per configuration."""
 import json
 import os
@@ -255,6 +256,105 @@ def repair_batch_cfg(k, m, d, sc, n, lost, loop_stripes, full):
         clay_amd.set_exec_mode(prev)
 
 
+def _encode_and_compare(c, data, par, scratch, flags, chunk):
+    """The only way to scrub without clay_scrub_device: encode into m scratch chunks, then compare
+    them with the stored parity (one device-side reduction per chunk into `flags`; torch.equal
+    would add a host synchronize per chunk)."""
+    c.encode_device(data, scratch, chunk, 0, stream.cuda_stream)
+    for j in range(c.m):
+        torch.any(scratch[j] != par[j], out=flags[j])
+
+
+def scrub_cfg(k, m, d, stripe, modes):
+    """One stripe: the scrub under each exec mode of `modes` ("auto": the line kernel for (4,2,5),
+    v1 elsewhere; "grouped": v1), the encode into scratch plus a device compare, and the encode
+    alone, samples alternated.  Bytes: the scrub reads n chunks; the encode reads k and writes m;
+    encode + compare moves k read + m written + 2m read."""
+    c = ClayCode(k, m, d)
+    chunk = c.encoded_chunk_size(stripe)
+    data, par = rnd(k, chunk, 11), torch.empty((m, chunk), dtype=torch.uint8, device="cuda")
+    dl, pl = [data[i] for i in range(k)], [par[i] for i in range(m)]
+    c.encode_device(dl, pl, chunk, 0, stream.cuda_stream)  # a codeword: the scrub's common case
+    scratch = torch.empty((m, chunk), dtype=torch.uint8, device="cuda")
+    sl = [scratch[i] for i in range(m)]
+    res = torch.empty(1, dtype=torch.int32, device="cuda")
+    flags = torch.empty(m, dtype=torch.bool, device="cuda")
+
+    def scrub(mode):
+        def fn():
+            clay_amd.set_exec_mode(mode)
+            c.scrub_device(dl, pl, res, chunk, 0, stream.cuda_stream)
+        return fn
+
+    prev = clay_amd.set_exec_mode("auto")
+    try:
+        fns = [scrub(mo) for mo in modes] + [lambda: _encode_and_compare(c, dl, pl, sl, flags, chunk),
+                                             lambda: c.encode_device(dl, sl, chunk, 0, stream.cuda_stream)]
+        out = timed_alternating(fns)
+        name = f"({k},{m},{d}) {stripe >> 20} MiB"
+        for mo, fn, (ms, mn) in zip(modes, fns, out):
+            fn()
+            torch.cuda.synchronize()
+            assert int(res.item()) == 0
+            report(f"scrub {name} {mo}", ms, mn, c.n * chunk, {"bytes_counted": "n chunks read"})
+        ms, mn = out[len(modes)]
+        assert not bool(flags.any().item())
+        report(f"scrub {name} by encode_device + compare", ms, mn, (k + 3 * m) * chunk,
+               {"bytes_counted": "k read + m written + 2m read", "path": clay_amd.last_encode_path(),
+                "scratch_bytes": m * chunk})
+        ms, mn = out[len(modes) + 1]
+        report(f"scrub {name} encode_device alone", ms, mn, c.n * chunk,
+               {"bytes_counted": "k read + m written", "path": clay_amd.last_encode_path()})
+    finally:
+        clay_amd.set_exec_mode(prev)
+
+
+def scrub_batch_cfg(k, m, d, stripe, n, loop_stripes):
+    """n stripes of `stripe` bytes of data per call (about 64 MiB): clay_scrub_device_strided in one
+    launch against a per-stripe loop of encode_device + compare on the same buffers (the first
+    loop_stripes stripes, reported per stripe; host and launch overhead included: that is what the
+    caller pays)."""
+    c = ClayCode(k, m, d)
+    chunk = c.encoded_chunk_size(stripe)
+    data = rnd(n * k, chunk, 12).view(n, k, chunk)
+    par = torch.empty((n, m, chunk), dtype=torch.uint8, device="cuda")
+    c.encode_device_strided(data, par, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+    res = torch.empty(n, dtype=torch.int32, device="cuda")
+    name = f"scrub ({k},{m},{d}) batch {n} x {stripe >> 10} KiB"
+    ms, mn = timed(lambda: c.scrub_device_strided(data, par, res, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream))
+    torch.cuda.synchronize()
+    assert not bool(res.any().item())
+    report(f"{name} one launch", ms, mn, n * c.n * chunk,
+           {"bytes_counted": "n chunks read", "per_stripe_us": round(ms * 1e3 / n, 6),
+            "stripe_data_GiBps": round(n * k * chunk / (ms * 1e-3) / 2**30, 1)})
+    nl = min(n, loop_stripes)
+    scratch = torch.empty((m, chunk), dtype=torch.uint8, device="cuda")
+    sl = [scratch[j] for j in range(m)]
+    flags = torch.empty((nl, m), dtype=torch.bool, device="cuda")
+    dls = [[data[s, i] for i in range(k)] for s in range(nl)]
+    pls = [[par[s, j] for j in range(m)] for s in range(nl)]
+
+    def loop():
+        for s in range(nl):
+            _encode_and_compare(c, dls[s], pls[s], sl, flags[s], chunk)
+
+    ts = []
+    for i in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        loop()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        if i >= 1:
+            ts.append(e0.elapsed_time(e1))
+    ms, mn = float(np.median(ts)), float(np.min(ts))
+    assert not bool(flags.any().item())
+    report(f"{name} per-stripe loop of {nl}: encode_device + compare", ms, mn, nl * (k + 3 * m) * chunk,
+           {"bytes_counted": "k read + m written + 2m read", "per_stripe_us": round(ms * 1e3 / nl, 4),
+            "path": clay_amd.last_encode_path(),
+            "stripe_data_GiBps": round(nl * k * chunk / (ms * 1e-3) / 2**30, 1)})
+
+
 def repair_cfg(k, m, d, chunk, lost):
     c = ClayCode(k, m, d)
     sc = chunk // c.sub_chunk_no
@@ -306,6 +406,13 @@ if __name__ == "__main__":
               ((4, 2, 5, 32, 65536, 0, 1024), (4, 2, 5, 320, 6553, 0, 1024), (4, 2, 5, 3200, 655, 0, 655),
                (4, 2, 5, 32768, 64, 0, 64), (10, 4, 13, 32, 585, 0, 585), (10, 4, 13, 320, 58, 0, 58),
                (9, 3, 11, 32, 2157, 0, 1024), (9, 3, 11, 320, 215, 0, 215))],
+            # ONLY=scrub: the scrub against the encode into scratch plus a compare
+            ("scrub", lambda: scrub_cfg(4, 2, 5, 64 << 20, ["auto", "grouped"])),
+            ("scrub", lambda: scrub_cfg(10, 4, 13, 1 << 30, ["auto"])),
+            ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 1 << 10, 65536, 1024)),
+            ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 10 << 10, 6553, 1024)),
+            ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 100 << 10, 655, 655)),
+            ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 1 << 20, 64, 64)),
             ("decode", lambda: decode_cfg(4, 2, 5, 64 << 20, [0])),
             ("decode", lambda: decode_cfg(10, 4, 13, 1 << 30, [0, 4, 8, 12])),
             ("decode", lambda: decode_cfg(10, 4, 13, 1 << 30, [0, 4, 8, 12], "grouped")),
