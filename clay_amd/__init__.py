@@ -124,7 +124,11 @@ def set_exec_mode(mode: str) -> str:
     'stream-local' or 'stream-fused2' (that kernel wherever it applies).  Modes choose kernels
     only: every mode returns the reference's bytes on any input.  The scrub of (4,2,5) runs the
     line kernel ('bs-scrub1') except under 'grouped' / 'tile', which keep the v1 kernel
-    ('bs-scrub') for A/B; every other mode scrubs as auto.  Returns the previous mode."""
+    ('bs-scrub') for A/B.  The scrub of (10,4,13) on 8-byte rows (sub-chunk a multiple of 8 and at
+    least 16 bytes, every chunk 8-byte aligned) runs the streaming kernel ('stream-scrub') under
+    'stream' at any size and under 'auto', 'stream-local' and 'stream-fused2' from a sub-chunk of
+    65,536 bytes up; 'grouped' / 'tile' keep v1 ('bs-scrub'), and so does every stripe off 8-byte
+    rows.  Every other scrub is the same in all modes.  Returns the previous mode."""
     if mode not in _EXEC_MODES:
         raise ValueError(f"unknown exec mode {mode!r}")
     prev = _lib.lib().clay_set_exec_mode(_EXEC_MODES[mode])
@@ -135,8 +139,9 @@ def last_exec_path() -> str:
     """Plan executor of this thread's last decode / repair / staged encode: 'tile' | 'grouped' |
     'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
     'bs-decode1-batch' (the batched decodes) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
-    (both) | the scrubs' 'bs-scrub1' / 'bs-scrub' (one launch per stripe) and 'bs-scrub1-batch' /
-    'bs-scrub-batch' (a batch in one launch) | 'none'."""
+    (both) | the scrubs' 'bs-scrub1' / 'bs-scrub' (one launch per stripe), 'bs-scrub1-batch' /
+    'bs-scrub-batch' (a batch in one launch) and 'stream-scrub' ((10,4,13) on the streaming kernel:
+    one launch per stripe in every entry point) | 'none'."""
     return _lib.lib().clay_last_exec_path().decode()
 
 
@@ -323,7 +328,8 @@ class ClayCode:
         buffers, parity_chunks: m, all read only; result: device memory of one uint32 (e.g. a
         torch.int32 tensor), defined by the call: bit j set iff parity chunk j differs from the
         encode of the data chunks.  A mismatch is a result, not an error.  Asynchronous on
-        `stream`.  Codes: (4,2,5), (6,3,8), (8,4,11), (9,3,11), (10,4,13)."""
+        `stream`.  Codes: (4,2,5), (6,3,8), (8,4,11), (9,3,11), (10,4,13).  (10,4,13) takes the
+        streaming kernel (last_exec_path 'stream-scrub') where set_exec_mode says so."""
         dp = (C.c_void_p * self.k)(*[_ptr(x) for x in data_chunks])
         pp = (C.c_void_p * self.m)(*[_ptr(x) for x in parity_chunks])
         err = ClayErrorStruct()
@@ -337,7 +343,9 @@ class ClayCode:
         """Scrub n_stripes stripes (clay.h clay_scrub_device_batch): stripe s uses
         data_chunks[s*k .. s*k+k) and parity_chunks[s*m .. s*m+m); result: n_stripes uint32 in
         device memory, one mask per stripe.  One launch where the stripes sit at uniform strides
-        (last_exec_path 'bs-scrub1-batch' / 'bs-scrub-batch'), else one per stripe."""
+        (last_exec_path 'bs-scrub1-batch' / 'bs-scrub-batch'), else one per stripe.  (10,4,13) on
+        the streaming kernel ('stream-scrub', see set_exec_mode; every stripe of the call must be
+        on 8-byte rows) is one launch per stripe: last_launch_count() == n_stripes."""
         dp = (C.c_void_p * max(1, self.k * n_stripes))(*[_ptr(x) for x in data_chunks])
         pp = (C.c_void_p * max(1, self.m * n_stripes))(*[_ptr(x) for x in parity_chunks])
         err = ClayErrorStruct()
@@ -352,7 +360,9 @@ class ClayCode:
                              parity_stripe_stride: int = 0, device: int = 0, stream: int = 0):
         """Scrub stripes at fixed strides in one launch (clay.h clay_scrub_device_strided).
         Strides default to a contiguous [n_stripes][k or m][chunk_size] layout; result:
-        n_stripes uint32 in device memory.  Allocates nothing: capturable unprepared."""
+        n_stripes uint32 in device memory.  Allocates nothing: capturable unprepared.  (10,4,13)
+        on the streaming kernel ('stream-scrub', see set_exec_mode; base and strides multiples of
+        8) is one launch per stripe."""
         dns = data_node_stride or chunk_size
         dss = data_stripe_stride or self.k * chunk_size
         pns = parity_node_stride or chunk_size

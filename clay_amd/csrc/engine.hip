@@ -1868,8 +1868,9 @@ static Error encode_device_impl(const clay_code_t *code, StripeOperands data, St
 
 // ---------------------------------------------------------------------------
 // Scrub: do the stored parity chunks match the encode of the stored data chunks?  The
-// compare-ending (SCRUB) instantiations of the two bit-sliced encode kernels (scrub_kernels.hip):
-// no scratch memory, no pointer table, nothing written but the result words.
+// compare-ending (SCRUB) instantiations of the two bit-sliced encode kernels and, for (10,4,13)
+// on 8-byte rows, of the streaming encode (scrub_kernels.hip): no scratch memory, no pointer
+// table, nothing written but the result words.
 // ---------------------------------------------------------------------------
 constexpr char kScrubCodes[] = "Invalid parameters: scrub has kernels for (4,2,5), (6,3,8), (8,4,11), (9,3,11) and (10,4,13) only";
 static bool scrub_code_ok(const clay_code_t &c) {
@@ -1933,6 +1934,54 @@ static Error launch_bs_scrub(CodeState &cs, const DevProps &prop, uint8_t *const
     return Error{};
 }
 
+// (10,4,13) on the compare-ending streaming encode (stream_encode.hpp SCRUB, scrub_kernels.hip):
+// one stripe per launch, launch_stream<10, 4>'s region / nslots arithmetic.  The caller has checked
+// the shape (stream_scrub_ok)
+static Error launch_stream_scrub(CodeState &cs, const DevProps &prop, uint8_t *const *data0, uint8_t *const *par0,
+                                 size_t sc, uint32_t *res, hipStream_t stream) {
+    using Kn = bs::StreamEnc<10, 4>;
+    using S = typename Kn::S;
+    if (Error e = rs_matches<S, 4>(cs)) return e;
+    // XCD region: sc / 8 rounded up to 32 bytes; one workgroup per CU
+    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
+    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
+    bs::BsArgs a{};
+    for (int i = 0; i < S::K; i++) a.data[i] = i < 10 ? data0[i] : nullptr;
+    for (int x = 0; x < 4; x++) a.par[x] = par0[x];
+    a.sc = sc;
+    a.tiles_per_xcd = region;
+    a.nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
+    a.ntiles = 0;
+    a.res = res;
+    CLAY_HIP(launch_stream_scrub_kernel(a, stream, prop.dev));
+    t_last_launches++;
+    return Error{};
+}
+
+// Auto's gate for the streaming scrub: the smallest sub-chunk from which it beat the v1 scrub at
+// that size and every larger one of the sweep (scripts/bench_paths.py ONLY=scrub_gate, DESIGN.md
+// 4.13, profiles/r11/scrub_stream.txt): 44.5 vs 68.6 us at 65,536, 92 vs 201 us at 131,072,
+// 309 vs 700 us at 419,432; at 32,768 v1 still leads (38.3 vs 39.2 us) and below it by 2x.  It
+// is also the derived bound: one full round of 256-byte tiles on every CU (8 XCDs x 32 workgroups
+// x 256 B), below which the streaming kernel cannot fill the chip.
+constexpr size_t kScrubStreamMinSc = 65536;
+
+// Can the streaming scrub take every stripe of the call?  (10,4,13), 8-byte rows (sc % 8 == 0 and
+// every data and parity chunk 8-byte aligned: for strided operands the base and both strides),
+// sc >= 16 (a clamped 16-byte piece), 32-bit chunk offsets.
+static bool stream_scrub_ok(const clay_code_t &c, const StripeOperands &data, const StripeOperands &par,
+                            size_t n_stripes, size_t sc) {
+    if (c.k != 10 || c.m != 4 || c.d != 13) return false;
+    if (sc % 8 != 0 || sc < 16 || double(256) * double(sc) >= 4294967296.0) return false;
+    auto rows8 = [&](const StripeOperands &f) {
+        if (f.strided)
+            return (reinterpret_cast<uintptr_t>(f.base) & 7u) == 0 && (f.node & 7) == 0 &&
+                   (n_stripes < 2 || (f.stripe & 7) == 0);
+        return !misaligned8(f.ptrs, n_stripes * f.per);
+    };
+    return rows8(data) && rows8(par);
+}
+
 // data / par: as encode_device_impl's, both read-only here.  result: n_stripes device words, every
 // one defined by the call (cleared on `stream` by the kernel's clear mode, then bit j of result[s] set iff
 // parity chunk j of stripe s differs from the encode of the stripe's data chunks).  batch_call:
@@ -1974,6 +2023,11 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
     const int xm = g_exec_mode.load(std::memory_order_relaxed);
     // (4,2,5): the line kernel; "grouped" / "tile" keep v1, its A/B partner
     const bool line = key == 402 && xm != kExecGrouped && xm != kExecTile;
+    // (10,4,13) on 8-byte rows: the streaming kernel, under "stream" at any size, under auto and the
+    // other streaming modes from kScrubStreamMinSc up; "grouped" / "tile" keep v1, its A/B partner.
+    // One path per call: every stripe of the call is eligible, or none takes it
+    const bool streamed = xm != kExecGrouped && xm != kExecTile && (xm == kExecStream || sc >= kScrubStreamMinSc) &&
+                          stream_scrub_ok(c, data, par, n_stripes, sc);
     auto launch = [&](uint8_t *const *d0, uint8_t *const *p0, int64_t sdata, int64_t spar, size_t ns, uint32_t *res,
                       bool *done) {
         if (line) return launch_bs_scrub1(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
@@ -2006,6 +2060,17 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
         }
     }
     std::vector<uint8_t *> d0(c.k), p0(c.m);
+    if (streamed) {
+        // one launch per stripe in every entry point (no one-launch batch on this kernel)
+        for (size_t s = 0; s < n_stripes; s++) {
+            data.stripe_ptrs(s, d0.data());
+            par.stripe_ptrs(s, p0.data());
+            e = launch_stream_scrub(cs, prop, d0.data(), p0.data(), sc, result + s, st);
+            if (e) return e;
+        }
+        t_last_exec = "stream-scrub";
+        return Error{};
+    }
     // stripes at one data and one parity stride: one launch, at any sub-chunk size (there is no
     // staged alternative that would pack small sub-chunks better)
     int64_t sdata = 0, spar = 0;

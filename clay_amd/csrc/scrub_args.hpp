@@ -14,6 +14,11 @@ hipError_t launch_bs_scrub1_kernel(int k, int m, bool bt, const bs::Enc1Args &a,
 // scrub_kernels.hip: k_bs_encode<.., SCRUB> (v1) for code (k, m) with d = k + m - 1, grid
 // a.nslots * 8; bt = byte tails.  hipErrorInvalidValue: no instantiation
 hipError_t launch_bs_scrub_kernel(int k, int m, bool bt, const bs::BsArgs &a, hipStream_t stream);
+// scrub_kernels.hip: k_stream_encode<10, 4 loaders, .., SCRUB> for (10,4,13), one stripe: the
+// streaming encode's arguments (a.tiles_per_xcd = XCD region bytes, grid a.nslots * 8) with a.res
+// set; rows 8-byte aligned, a.sc % 8 == 0, a.sc >= 16, 256 * a.sc < 2^32.  Sets the kernel's
+// dynamic-LDS attribute once per device `dev`
+hipError_t launch_stream_scrub_kernel(const bs::BsArgs &a, hipStream_t stream, int dev);
 
 // The one column-group count (PG) per code the v1 scrub is instantiated with: the host sizes
 // tiles and slots from BsKernel<KD, M, ScrubPg<KD, M>::value>

@@ -2,9 +2,14 @@
 // the bit-sliced encode kernels: k_bs_encode1 (bitslice_line.hpp) for (4,2,5) and k_bs_encode
 // (bitslice.hpp, v1) for (4,2), (6,3), (8,4), (9,3) and (10,4) with d = n - 1, each with and
 // without byte tails.  Same kernels as the encodes up to the last step, which loads the stored
-// parity and compares where the encode stores.
+// parity and compares where the encode stores.  And the compare-ending variant of the streaming
+// encode k_stream_encode (stream_encode.hpp) for (10,4,13).
+#include <mutex>
+#include <set>
+
 #include "bitslice_line.hpp"
 #include "scrub_args.hpp"
+#include "stream_encode.hpp"
 
 namespace clay {
 
@@ -37,6 +42,27 @@ hipError_t launch_bs_scrub_kernel(int k, int m, bool bt, const bs::BsArgs &a, hi
     case 1004: return launch_v1<10, 4>(bt, a, stream);
     default: return hipErrorInvalidValue;
     }
+}
+
+// The compare-ending k_stream_encode of (10,4,13): the library's encode instantiation (4 loader
+// waves, lane map kStreamEncMap) with SCRUB.  No LOADERS == 0 variant: its counted vmcnt waits
+// count the parity stores of the previous two steps.
+hipError_t launch_stream_scrub_kernel(const bs::BsArgs &a, hipStream_t stream, int dev) {
+    using Kn = bs::StreamEnc<10, 4>;
+    constexpr auto kern = &bs::k_stream_encode<10, 4, 0, bs::kStreamEncMap, true>;
+    static std::mutex mu;
+    static std::set<int> done;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!done.count(dev)) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
+            if (e != hipSuccess) return e;
+            done.insert(dev);
+        }
+    }
+    kern<<<dim3(a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
+    return hipGetLastError();
 }
 
 }  // namespace clay

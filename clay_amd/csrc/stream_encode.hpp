@@ -68,6 +68,21 @@ __device__ __forceinline__ void dma16_masked(uint32_t lds_addr, const uint8_t *s
         : "memory");
 }
 
+// Two 16-byte loads (SGPR base + per-lane 32-bit offsets) of the lanes in `mask` only (StreamEnc
+// SCRUB): EXEC is set inside the statement, so there is no branch around the pair -- with any lane
+// in the mask both instructions issue, which the caller's counted waits rely on -- and a masked
+// lane issues no access and keeps what lo / hi held.  Hidden from the compiler's waitcnt pass: the
+// caller waits with a counted s_waitcnt vmcnt before using lo / hi.
+__device__ __forceinline__ void ld16s2_masked(u32x4 &lo, u32x4 &hi, const uint8_t *sbase, uint32_t voff_lo, uint32_t voff_hi,
+                                              uint64_t mask) {
+    uint64_t ex;
+    asm volatile(
+        "s_mov_b64 %2, exec\n\ts_mov_b64 exec, %6\n\t"
+        "global_load_dwordx4 %0, %3, %5\n\tglobal_load_dwordx4 %1, %4, %5\n\ts_mov_b64 exec, %2"
+        : "+v"(lo), "+v"(hi), "=&s"(ex)
+        : "v"(voff_lo), "v"(voff_hi), "s"(sbase), "s"(mask));
+}
+
 // (k_stream_encode's own tile map is BalancedMap, stream_tile_map.hpp; StreamMap serves the other
 // streaming kernels and the probe's old-map builds, PROBE 2097152)
 // XCD x owns bytes [x * region, min((x + 1) * region, sc)); full W-byte tiles round robin over
@@ -125,8 +140,11 @@ struct ChipMap {
 // with the light waves 0-3, for A/B)
 // LPRED (probe builds only): a tile narrower than 256 whose width is a multiple of 16 loads with
 // the lanes past its end masked off (dma16_masked) instead of with clamped addresses
+// SCRUB: the compare-ending variant (scrub_kernels.hip): the same kernel up to the outputs, which
+// load the stored parity where the encode stores and compare (fetch / check); `sink` then carries
+// the lane's mismatch bits (bit x = parity node x) and nothing is written but a.res
 template <int KD, int LOADERS, int CPL = 0, int CPS = 0, bool CSE = true, bool SINK = false, bool CHECK = false,
-          int MAP = 0, bool LPRED = false>
+          int MAP = 0, bool LPRED = false, bool SCRUB = false>
 struct StreamEnc {
     using K6 = EncMath<KD>;
     using S = typename K6::S;
@@ -579,6 +597,86 @@ struct StreamEnc {
             }
         }
     }
+    // ---------------- compute: compare-ending outputs (SCRUB) ----------------
+    // What the scrub does where the encode has put<X>, in two halves so that the loads of one
+    // output are in flight during the transposes and the compare of the output before it
+    // (end_group).  fetch<X> loads the stored parity at exactly the bytes put<X> would store in
+    // its DPP pair, at the same addresses and under the same lane predicate: a lane the encode
+    // masks off issues no load (in a narrow tile its computed words come from clamped piece
+    // addresses and belong to another tile's positions; in the chunk's last row its address can
+    // lie past the chunk) and keeps zeros.  The two loads are one asm statement (ld16s2_masked:
+    // hidden from the compiler's waitcnt pass, which would wait vmcnt(0) at the first use); check<X>
+    // waits for them with a counted vmcnt (AFTER = VMEM instructions issued behind them), compares
+    // and ORs bit X into `bad` when any stored bit differs.  With dedicated loader waves a compute
+    // wave issues no other VMEM, and lds_barrier() leaves loads in flight.  The one ragged tile of a
+    // stripe is not pipelined: fetch loads nothing there (an empty mask) and check loads the 16 or 8
+    // bytes put<X> stores with plain loads.
+    struct Stored {
+        u32x4 lo, hi;  // the rows lo and hi of put's DPP pair
+    };
+    // 16 / 8 stored bytes in global memory at an 8-byte aligned address (rows are 8-byte aligned)
+    typedef uint32_t ld4_t __attribute__((ext_vector_type(4), aligned(8)));
+    typedef uint32_t ld2_t __attribute__((ext_vector_type(2), aligned(8)));
+    typedef const __attribute__((address_space(1))) ld4_t *gld4_p;
+    typedef const __attribute__((address_space(1))) ld2_t *gld2_p;
+    // the lane's position in the tile (DPP-pair path), as in put
+    __device__ __forceinline__ static uint32_t pair_pos(uint32_t prel, bool odd) {
+        uint32_t pos = prel + (odd ? 128u : 0u);
+        if constexpr (!PSWAP) {
+            uint32_t l = threadIdx.x;
+            asm volatile("" : "+v"(l));
+            pos = (l & 15u) << 4;  // part = lane bits 0-2, odd = bit 3
+        }
+        return pos;
+    }
+    template <int X>
+    __device__ __forceinline__ static Stored fetch(const BsArgs &a, uint32_t z, StreamTile t, uint32_t prel, bool ragged) {
+        Stored s;
+        s.lo = u32x4{0u, 0u, 0u, 0u};
+        s.hi = u32x4{0u, 0u, 0u, 0u};
+        const bool odd = PSWAP ? ((threadIdx.x >> 4) & 1u) : ((threadIdx.x >> 3) & 1u);
+        uint32_t off = (z - (odd ? PAIR : 0u)) * uint32_t(a.sc);
+        asm volatile("" : "+v"(off));  // keep the 16 (node, layer) offsets out of LICM
+        const uint32_t pos = pair_pos(prel, odd);
+        off += t.b0 + pos;
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(!ragged && pos + 16u <= t.vend - t.b0);
+        ld16s2_masked(s.lo, s.hi, uniform_ptr(a.par[X]), off, off + PAIR * uint32_t(a.sc), mask);
+        return s;
+    }
+    template <int X, int AFTER>
+    __device__ __forceinline__ static void check(const BsArgs &a, uint32_t (&cv)[8], Stored &s, uint32_t z, StreamTile t,
+                                                 uint32_t prel, bool ragged, uint32_t &bad) {
+        transpose8(cv);
+        const bool odd = PSWAP ? ((threadIdx.x >> 4) & 1u) : ((threadIdx.x >> 3) & 1u);
+        uint32_t lo[4], hi[4];
+        pair_halves(cv, lo, hi);  // every lane takes part in the exchange, masked or not
+        // s has landed once at most AFTER younger VMEM instructions are outstanding; the operands
+        // tie every use of s behind the wait
+        asm volatile("s_waitcnt vmcnt(%2)" : "+v"(s.lo), "+v"(s.hi) : "n"(AFTER));
+        uint32_t x = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) x |= (s.lo[i] ^ lo[i]) | (s.hi[i] ^ hi[i]);
+        if (pair_pos(prel, odd) + 16u > t.vend - t.b0) x = 0;  // a masked lane: no part in the compare
+        if (ragged) {
+            // the bytes the encode stores plainly: 16 when nv == 16, 8 when nv >= 8, nothing otherwise
+            x = 0;
+            const uint8_t *p = a.par[X] + uint64_t(z) * a.sc + t.b0 + prel;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t pos = t.b0 + prel + 128u * uint32_t(h);
+                const uint32_t nv = pos >= t.vend ? 0u : (t.vend - pos >= 16u ? 16u : t.vend - pos);
+                if (nv == 16u) {
+                    const ld4_t v = *(gld4_p)(p + 128 * h);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) x |= v[i] ^ cv[4 * h + i];
+                } else if (nv >= 8u) {
+                    const ld2_t v = *(gld2_p)(p + 128 * h);
+                    x |= (v[0] ^ cv[4 * h]) | (v[1] ^ cv[4 * h + 1]);
+                }
+            }
+        }
+        bad |= x ? 1u << X : 0u;
+    }
     // Group G finished: red vertex C[G][z_G] = U, and the PFT pairs with groups h < G
     // (transforms.rs:108-125) (Hold: encode_math.hpp).  Force-inlined: called out of line
     // (several instantiations in one translation unit), acc and Hold would go through scratch.
@@ -589,7 +687,18 @@ struct StreamEnc {
         uint32_t cv[8];
 #pragma unroll
         for (int w = 0; w < 8; w++) cv[w] = acc[G * 8 + w];
-        put<G>(a, cv, zg, t, prel, ragged, sink);
+        // SCRUB: the outputs form a chain, C[G][z_G] and then C[h][z_G], C[G][z_h] of every pair; the
+        // stored parity of an output is fetched before the transposes and the compare of the output
+        // before it, and the first fetch of a pair's before its PFT.  (cv, ps): the pending output,
+        // always of parity node G, at layer zp
+        [[maybe_unused]] Stored ps;
+        [[maybe_unused]] uint32_t zp = zg;
+        if constexpr (SCRUB) {
+            ps = fetch<G>(a, zg, t, prel, ragged);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            put<G>(a, cv, zg, t, prel, ragged, sink);
+        }
         auto pair = [&](const uint32_t *uh_at_g, const uint32_t *ug_at_h, auto hc) BS_INL {
             constexpr int h = decltype(hc)::value;
             const uint32_t zh = uint32_t(c * 4 + h);
@@ -612,8 +721,20 @@ struct StreamEnc {
                 c1[w] = c12[w];
                 c2[w] = c12[8 + w];
             }
-            put<h>(a, c1, zg, t, prel, ragged, sink);  // C[h][z_G]
-            put<G>(a, c2, zh, t, prel, ragged, sink);  // C[G][z_h]
+            if constexpr (SCRUB) {
+                Stored s1 = fetch<h>(a, zg, t, prel, ragged);  // C[h][z_G]
+                __builtin_amdgcn_sched_barrier(0);
+                check<G, 2>(a, cv, ps, zp, t, prel, ragged, sink);  // the pending output; s1 is behind it
+                ps = fetch<G>(a, zh, t, prel, ragged);  // C[G][z_h]
+                __builtin_amdgcn_sched_barrier(0);
+                check<h, 2>(a, c1, s1, zg, t, prel, ragged, sink);
+                zp = zh;
+#pragma unroll
+                for (int w = 0; w < 8; w++) cv[w] = c2[w];
+            } else {
+                put<h>(a, c1, zg, t, prel, ragged, sink);  // C[h][z_G]
+                put<G>(a, c2, zh, t, prel, ragged, sink);  // C[G][z_h]
+            }
         };
         auto keep = [&](int ri, int p) BS_INL {
 #pragma unroll
@@ -636,6 +757,7 @@ struct StreamEnc {
             pair(acc + 8, H.r[3], std::integral_constant<int, 1>{});   // U[3][z1]
             pair(acc + 16, H.r[1], std::integral_constant<int, 2>{});  // U[3][z2]
         }
+        if constexpr (SCRUB) check<G, 0>(a, cv, ps, zp, t, prel, ragged, sink);  // the last pending output
     }
 };
 
@@ -700,11 +822,16 @@ struct TimeAcc {
 // 0.3484-0.3489 for the round-5 kernel)
 constexpr int kStreamEncMap = 8;
 
-template <int KD, int LOADERS, int PROBE = 0, int MAP = 0>
+// SCRUB: the compare-ending variant (StreamEnc SCRUB; the library's scrub of (10,4,13),
+// scrub_kernels.hip): data and parity are read-only, a compute wave that saw a mismatch ORs its
+// bits into a.res[0] after its last tile; loader waves and workgroups without a tile never touch
+// a.res.  Only with dedicated loader waves: the counted waits of LOADERS == 0 count parity stores.
+template <int KD, int LOADERS, int PROBE = 0, int MAP = 0, bool SCRUB = false>
 __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_encode(BsArgs a) {
+    static_assert(!SCRUB || (LOADERS > 0 && PROBE == 0), "the scrub variant: loader waves, no probe bits");
     using Kn = StreamEnc<KD, LOADERS, (PROBE >> 6) & 3, (PROBE >> 8) & 3, ((PROBE >> 10) & 1) == 0, (PROBE & 262144) != 0,
-                         (PROBE & 524288) != 0, MAP, (PROBE & 4194304) != 0>;
-    uint32_t sink = 0;  // SINK probes only
+                         (PROBE & 524288) != 0, MAP, (PROBE & 4194304) != 0, SCRUB>;
+    uint32_t sink = 0;  // SINK probes; SCRUB: the lane's mismatch bits
     constexpr bool TM = (PROBE & 4096) != 0;
     using K6 = typename Kn::K6;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -916,6 +1043,7 @@ __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_enco
     if constexpr (DEFER) {
         if (pend >= 0) end_any(pend, pt);
     }
+    if constexpr (SCRUB) scrub_report<4>(a.res, sink);  // every compute wave, in uniform control flow
     if constexpr ((PROBE & 262144) != 0) {
         // a.sdata is 0 in the probe: the predicate is (almost) never true, but not foldable
         if (sink == uint32_t(a.sdata) + 0x9E3779B9u) a.par[0][threadIdx.x] = uint8_t(sink);

@@ -186,7 +186,14 @@ int clay_encode_device_strided(const clay_code_t *code, const uint8_t *data, int
  * (10,4,13); any other code is CLAY_ERR_INVALID_PARAMETERS.  Validation is
  * clay_encode_device's; a NULL result is CLAY_ERR_INVALID_PARAMETERS.  Last exec path
  * "bs-scrub1" ((4,2,5); k_bs_encode1) or "bs-scrub" (k_bs_encode; (4,2,5) under exec modes
- * 1 / 2).  clay_set_encode_path has no effect. */
+ * 1 / 2).  clay_set_encode_path has no effect.
+ * (10,4,13) at streaming speed: a stripe on 8-byte rows -- sub-chunk size a multiple of 8 and at
+ * least 16 (and 256 x sub-chunk < 2^32), every data and parity chunk 8-byte aligned -- runs the
+ * compare-ending variant of the streaming encode k_stream_encode, last exec path "stream-scrub":
+ * under exec mode 3 stream at any such sub-chunk, under 0 auto, 5 and 6 from a sub-chunk of
+ * 65,536 bytes (one full round of 256-byte tiles on every CU; below it v1 is faster).  Exec
+ * modes 1 / 2 keep v1 ("bs-scrub"), its A/B partner, and so does every stripe off 8-byte rows in
+ * every mode.  The 1 GiB stripe: 0.32 ms against 0.70 on v1 (the encode: 0.33). */
 int clay_scrub_device(const clay_code_t *code, const uint8_t *const *data_chunks,
                       const uint8_t *const *parity_chunks, size_t chunk_size, uint32_t *result,
                       int device, void *stream, clay_error_t *err);
@@ -196,16 +203,21 @@ int clay_scrub_device(const clay_code_t *code, const uint8_t *const *data_chunks
  * the mask of stripe s, every word defined by the call.  Stripes that sit at one data and
  * one parity stride (rows of one buffer) run in ONE launch at any sub-chunk size (last exec
  * path "bs-scrub1-batch" / "bs-scrub-batch"); any other arrangement takes one launch per
- * stripe ("bs-scrub1" / "bs-scrub", clay_last_launch_count = n_stripes).  n_stripes = 0
- * returns CLAY_OK and touches nothing. */
+ * stripe ("bs-scrub1" / "bs-scrub", clay_last_launch_count = n_stripes).  (10,4,13) on the
+ * streaming kernel (see clay_scrub_device; EVERY stripe of the call must be on 8-byte rows,
+ * else none takes it: one path per call) has no one-launch batch: "stream-scrub" is one launch
+ * per stripe in the batch and strided forms too, clay_last_launch_count = n_stripes.
+ * n_stripes = 0 returns CLAY_OK and touches nothing. */
 int clay_scrub_device_batch(const clay_code_t *code, const uint8_t *const *data_chunks,
                             const uint8_t *const *parity_chunks, uint32_t *result, size_t n_stripes,
                             size_t chunk_size, int device, void *stream, clay_error_t *err);
 
 /* Batched scrub of stripes at fixed strides, the layout of clay_encode_device_strided: data
  * node i of stripe s at data + s*data_stripe_stride + i*data_node_stride, parity node j at
- * parity + s*parity_stripe_stride + j*parity_node_stride.  Always one launch, O(1) host
- * work.  Bytes between the chunks are never read into the answer. */
+ * parity + s*parity_stripe_stride + j*parity_node_stride.  One launch, O(1) host work --
+ * except (10,4,13) on the streaming kernel ("stream-scrub": both bases and all four strides
+ * multiples of 8), one launch per stripe.  Bytes between the chunks are never read into the
+ * answer. */
 int clay_scrub_device_strided(const clay_code_t *code, const uint8_t *data, int64_t data_node_stride,
                               int64_t data_stripe_stride, const uint8_t *parity, int64_t parity_node_stride,
                               int64_t parity_stripe_stride, uint32_t *result, size_t n_stripes,
@@ -448,7 +460,9 @@ int clay_set_encode_path(int mode);
  *    of (9,3,11) / (10,4,13); last path "bs-repair-stream"), else k_bs_repair ("bs-repair"))
  *   (scrubs, clay_scrub_device*: (4,2,5) on the line kernel, "bs-scrub1" / "bs-scrub1-batch",
  *    except under 1 grouped and 2 tile, which keep v1, "bs-scrub" / "bs-scrub-batch", its A/B
- *    partner; every other code on v1 in every mode)
+ *    partner; (10,4,13) on 8-byte rows on the streaming kernel, "stream-scrub", under 3 stream
+ *    at any sub-chunk and under 0 auto / 5 / 6 from a sub-chunk of 65,536 bytes, v1 under 1 / 2;
+ *    everything else on v1 in every mode)
  *   3 stream  -- every decode a streaming kernel takes on it: the local decode where it takes
  *                the pattern (the (2,1) patterns: the fused decode v2 first), else the fused
  *                decode v2 (2-4 erasures, at most two per section); everything else as auto
@@ -474,7 +488,8 @@ int clay_set_exec_mode(int mode);
  * stripes), the batched repairs' "bs-repair-batch" (k_bs_repair over many stripes), both batches'
  * "grouped-batch" (k_gexec over many stripes), the scrubs' "bs-scrub1" (k_bs_encode1's compare
  * ending) / "bs-scrub" (k_bs_encode's) with one launch per stripe and "bs-scrub1-batch" /
- * "bs-scrub-batch" (a batch in one launch), or "none". */
+ * "bs-scrub-batch" (a batch in one launch) and "stream-scrub" (k_stream_encode's compare ending,
+ * (10,4,13): one launch per stripe in every entry point), or "none". */
 const char *clay_last_exec_path(void);
 
 /* Name of the path the last encode on this thread used ("fused-q4w128p8", "staged", ...). */

@@ -4,7 +4,8 @@ HBM, HIP events on the launch stream, median of N runs).  Algorithmic bytes per 
 encode  read k*chunk + write m*chunk
 decode  read (n-e)*chunk + write (#erased data nodes)*chunk
 repair  read d*beta*sc + write chunk
-scrub   read n*chunk (ONLY=scrub)
+scrub   read n*chunk (ONLY=scrub; scrub10: the (10,4,13) 1 GiB leg alone; scrub_gate: the sweep behind
+        auto's gate for the streaming scrub)
 Prints one JSON object per configuration."""
 import json
 import os
@@ -267,7 +268,8 @@ def _encode_and_compare(c, data, par, scratch, flags, chunk):
 
 def scrub_cfg(k, m, d, stripe, modes):
     """One stripe: the scrub under each exec mode of `modes` ("auto": the line kernel for (4,2,5),
-    v1 elsewhere; "grouped": v1), the encode into scratch plus a device compare, and the encode
+    the streaming kernel for (10,4,13) above its gate, v1 elsewhere; "stream": the streaming kernel
+    for (10,4,13); "grouped": v1), the encode into scratch plus a device compare, and the encode
     alone, samples alternated.  Bytes: the scrub reads n chunks; the encode reads k and writes m;
     encode + compare moves k read + m written + 2m read."""
     c = ClayCode(k, m, d)
@@ -306,6 +308,63 @@ def scrub_cfg(k, m, d, stripe, modes):
         report(f"scrub {name} encode_device alone", ms, mn, c.n * chunk,
                {"bytes_counted": "k read + m written", "path": clay_amd.last_encode_path()})
     finally:
+        clay_amd.set_exec_mode(prev)
+
+
+def scrub_gate_cfg(sizes=(2048, 8192, 16384, 32768, 65536, 131072, 419432), samples=5):
+    """ONLY=scrub_gate: where does the streaming scrub of (10,4,13) overtake v1?  For every
+    sub-chunk size, one stripe with a codeword in the buffers scrubbed under "stream"
+    (stream-scrub) and under "grouped" (bs-scrub), `samples` samples each of B2B back-to-back
+    calls, alternated.  A win: the streaming median is below v1's by more than the spread
+    (max - min) of the v1 samples of the same call.  Auto's gate (engine.hip kScrubStreamMinSc) is
+    the smallest size from which it wins at that size and every larger one."""
+    global RUNS
+    c = ClayCode(10, 4, 13)
+    keep, RUNS = RUNS, samples
+    prev = clay_amd.set_exec_mode("auto")
+    try:
+        for sc in sizes:
+            chunk = c.sub_chunk_no * sc
+            data, par = rnd(10, chunk, 13), torch.empty((4, chunk), dtype=torch.uint8, device="cuda")
+            dl, pl = [data[i] for i in range(10)], [par[i] for i in range(4)]
+            c.encode_device(dl, pl, chunk, 0, stream.cuda_stream)
+            res = torch.empty(1, dtype=torch.int32, device="cuda")
+            paths, ts = [], [[], []]
+
+            def scrub(mode):
+                def fn():
+                    clay_amd.set_exec_mode(mode)
+                    c.scrub_device(dl, pl, res, chunk, 0, stream.cuda_stream)
+                return fn
+
+            fns = [scrub("stream"), scrub("grouped")]
+            for j, fn in enumerate(fns):
+                res.fill_(-1)
+                fn()
+                torch.cuda.synchronize()
+                assert int(res.item()) == 0
+                paths.append(clay_amd.last_exec_path())
+            for i in range(RUNS + 2):
+                for j, fn in enumerate(fns):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    fn()
+                    e0.record(stream)
+                    for _ in range(B2B):
+                        fn()
+                    e1.record(stream)
+                    torch.cuda.synchronize()
+                    if i >= 2:
+                        ts[j].append(e0.elapsed_time(e1) / B2B)
+            s_med, v_med = float(np.median(ts[0])), float(np.median(ts[1]))
+            v_spread = float(np.max(ts[1]) - np.min(ts[1]))
+            print(json.dumps({"config": f"scrub gate (10,4,13) sc {sc}", "paths": paths,
+                              "stream_us": [round(t * 1e3, 2) for t in ts[0]],
+                              "v1_us": [round(t * 1e3, 2) for t in ts[1]],
+                              "stream_median_us": round(s_med * 1e3, 2), "v1_median_us": round(v_med * 1e3, 2),
+                              "v1_spread_us": round(v_spread * 1e3, 2),
+                              "stream_wins": bool(v_med - s_med > v_spread)}), flush=True)
+    finally:
+        RUNS = keep
         clay_amd.set_exec_mode(prev)
 
 
@@ -408,7 +467,10 @@ if __name__ == "__main__":
                (9, 3, 11, 32, 2157, 0, 1024), (9, 3, 11, 320, 215, 0, 215))],
             # ONLY=scrub: the scrub against the encode into scratch plus a compare
             ("scrub", lambda: scrub_cfg(4, 2, 5, 64 << 20, ["auto", "grouped"])),
-            ("scrub", lambda: scrub_cfg(10, 4, 13, 1 << 30, ["auto"])),
+            ("scrub", lambda: scrub_cfg(10, 4, 13, 1 << 30, ["auto", "stream", "grouped"])),
+            ("scrub10", lambda: scrub_cfg(10, 4, 13, 1 << 30, ["auto", "stream", "grouped"])),
+            # ONLY=scrub_gate: the sweep behind auto's gate for the streaming scrub
+            ("scrub_gate", scrub_gate_cfg),
             ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 1 << 10, 65536, 1024)),
             ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 10 << 10, 6553, 1024)),
             ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 100 << 10, 655, 655)),
