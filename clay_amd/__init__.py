@@ -99,6 +99,10 @@ def set_encode_path(mode: str, tile: int = 0) -> str:
     `tile` selects a variant: 'bitsliced' lanes per column group (0, 1, 4), 'stream' loader
     waves for (10,4,13) (0 = default 4, 1, 2, 4; (9,4,12) always runs 4; (9,3,11) 2, or 7 for
     variant 7). 'stream' (10,4,13) / (9,4,12) needs 8-byte rows (sc % 8 == 0).
+    Batched calls of those two codes (2 or more stripes at uniform strides on 8-byte rows) are one
+    launch of the streaming kernel ('stream-batch-k10m4-w256-l4' / 'stream-batch-k9m4-w256-l4')
+    under 'stream' with variant 0 or 4 at any size, and under 'auto' for stripes of more than 4 MiB
+    of data with sub-chunks up to 262,152 bytes; variants 1 / 2 keep one launch per stripe.
     Every accepted path produces the reference's parity; anything else raises ValueError.
     Returns the previous path name."""
     if mode not in _ENCODE_PATHS:

@@ -225,7 +225,11 @@ struct BsArgs {
     uint64_t sc;                     // sub-chunk bytes (v1: any; bs6 / stream: multiple of 8)
     uint32_t ntiles, tiles_per_xcd, nslots;
     // k_bs_encode batches: stripe s's nodes at data[i] + s * sdata, par[x] + s * spar
-    // (ntiles tiles per stripe, tiles_per_xcd over all nstripes * ntiles); 0 = one stripe
+    // (ntiles tiles per stripe, tiles_per_xcd over all nstripes * ntiles); 0 = one stripe.
+    // k_stream_encode BATCH (stream_batch_kernels.hip): the same nstripes / sdata / spar;
+    // tiles_per_xcd = one stripe's XCD region, nslots = one stripe's workgroups per XCD and
+    // ntiles = the groups of nslots workgroups per XCD (grid = 8 * ntiles * nslots; the other
+    // k_stream_encode instantiations ignore ntiles)
     uint32_t nstripes;
     int64_t sdata, spar;
     // SCRUB instantiations: result word of stripe 0 (stripe s ORs its mismatch bits into res[s]);

@@ -1796,6 +1796,79 @@ static Error encode_bs_batch(CodeState &cs, int dev, const StripeOperands &data,
     }
 }
 
+hipError_t launch_stream_batch_kernel(int kd, const bs::BsArgs &a, hipStream_t stream, int dev);  // stream_batch_kernels.hip
+
+// Batched streaming encode (k_stream_encode BATCH, stream_batch_kernels.hip) for (10,4,13) and
+// (9,4,12): ONE launch for ns >= 2 stripes at uniform strides.  Every stripe keeps launch_stream's
+// cut (region, nsS workgroups per XCD); the per_xcd workgroups of an XCD form G groups of nsS, and
+// group j runs stripes j, j + G, ... back to back (BatchMap, stream_tile_map.hpp).  No allocation,
+// no pointer table: stripe 0's pointers and the two strides travel in the kernel arguments.
+// Anything it does not take (a chunk off the stride, rows off 8-byte alignment, odd sc) leaves
+// *done false and the caller goes on as before.
+template <int KD>
+static Error launch_stream_batch(CodeState &cs, const DevProps &prop, const StripeOperands &data, const StripeOperands &par,
+                                 size_t ns, size_t sc, hipStream_t stream, bool *done) {
+    using Kn = bs::StreamEnc<KD, 4>;
+    using S = typename Kn::S;
+    // 8-byte rows, a clamped 16-byte piece, 32-bit chunk offsets in the lanes
+    if (sc % 8 != 0 || sc < 16 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
+    if (ns < 2 || ns > 0xFFFFFFFFull) return Error{};
+    // stripe-0 pointers and one stride for all data nodes, one for all parity nodes
+    int64_t sdata = 0, spar = 0;
+    if (!uniform_stride(data, 0, ns, nullptr, size_t(KD), &sdata) || !uniform_stride(par, 0, ns, nullptr, 4, &spar))
+        return Error{};
+    uint8_t *d0[KD], *p0[4];
+    data.stripe_ptrs(0, d0);
+    par.stripe_ptrs(0, p0);
+    if (misaligned8(d0, size_t(KD), sdata) || misaligned8(p0, 4, spar)) return Error{};
+    if (Error e = rs_matches<S, 4>(cs)) return e;
+    // one stripe's cut, as launch_stream; G groups of nslots workgroups per XCD
+    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
+    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
+    const uint32_t nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
+    const uint32_t groups = bs::batch_groups(per_xcd, nslots, uint32_t(ns));
+    // a workgroup's steps (12 per tile) are counted in an int: rounds per stripe x stripes per group
+    const uint64_t rounds = (uint64_t(region) + uint64_t(nslots) * 256u - 1u) / (uint64_t(nslots) * 256u);
+    if (rounds * ((ns + groups - 1) / groups) * uint64_t(Kn::STEPS) > 0x7FFFFFFFull) return Error{};
+    bs::BsArgs a{};
+    for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? d0[i] : nullptr;
+    for (int x = 0; x < 4; x++) a.par[x] = p0[x];
+    a.sc = sc;
+    a.tiles_per_xcd = region;
+    a.nslots = nslots;
+    a.ntiles = groups;
+    a.nstripes = uint32_t(ns);
+    a.sdata = sdata;
+    a.spar = spar;
+    CLAY_HIP(launch_stream_batch_kernel(KD, a, stream, prop.dev));
+    t_last_launches++;
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), "stream-batch-k%dm4-w256-l4", KD);
+    t_last_path = buf;
+    *done = true;
+    return Error{};
+}
+// Auto's upper gate for the streaming batch: the largest sub-chunk of the sweep at which the batch
+// beat the per-stripe loop at that size and every smaller one, for 2, 3, 4 and 6 stripes
+// (scripts/bench_paths.py ONLY=batch_stream_gate, DESIGN.md 4.4, profiles/r12/batch_stream_gate.txt;
+// a win: the batch's median below the loop's by more than the spread of the loop's samples).  From
+// 65,536 bytes up one stripe fills the chip (one group), so the batch only saves the seams between
+// launches, 3-7 us each: 6 stripes 386 vs 425 us at 66,176, 671 vs 697 us at 131,080, 1,182 vs
+// 1,202 us at 262,152.  At 419,432 (the benchmark's sub-chunk, seven rounds per stripe) 2 to 4
+// stripes tie within the spread and 6 stripes lose (1,904 vs 1,881 us), so auto keeps the loop there.
+constexpr size_t kStreamBatchMaxSc = 262152;
+
+static Error encode_stream_batch(CodeState &cs, int dev, const StripeOperands &data, const StripeOperands &par, size_t ns,
+                                 size_t chunk, hipStream_t stream, bool *done) {
+    *done = false;
+    const clay_code_t &c = cs.code;
+    if (c.m != 4 || c.d != c.k + 3 || (c.k != 10 && c.k != 9)) return Error{};
+    const size_t sc = chunk / c.sub_chunk_no;
+    const DevProps &prop = dev_props(dev);
+    return c.k == 10 ? launch_stream_batch<10>(cs, prop, data, par, ns, sc, stream, done)
+                     : launch_stream_batch<9>(cs, prop, data, par, ns, sc, stream, done);
+}
+
 // data / par: the k data and m parity operands of every stripe, both in the same form (their
 // `per` is set here, once the code is known to be one)
 static Error encode_device_impl(const clay_code_t *code, StripeOperands data, StripeOperands par, size_t n_stripes,
@@ -1836,6 +1909,17 @@ static Error encode_device_impl(const clay_code_t *code, StripeOperands data, St
         e = encode_bs_batch(cs, dev, data, par, n_stripes, chunk, st, &done);
         if (e || done) return e;
         return encode_staged_batch(cs, *ds, dev, data, par, n_stripes, chunk, st);
+    }
+    // several stripes of (10,4,13) / (9,4,12) where the streaming kernel would run once per stripe
+    // (auto: stripes above the staged batch's size, sub-chunks up to kStreamBatchMaxSc; "stream" with
+    // its default loaders: any size): one launch of its batch variant, when the stripes sit at
+    // uniform strides on 8-byte rows
+    if (n_stripes >= 2 && ((mode == kModeAuto && code->k * chunk > kBatchMaxStripeBytes &&
+                            chunk / code->sub_chunk_no <= kStreamBatchMaxSc) ||
+                           (mode == kModeStream && (tile == 0 || tile == 4)))) {
+        bool done = false;
+        e = encode_stream_batch(cs, dev, data, par, n_stripes, chunk, st, &done);
+        if (e || done) return e;
     }
     // the per-stripe kernels below take pointer arrays
     std::vector<uint8_t *> dv, pv;

@@ -143,8 +143,12 @@ struct ChipMap {
 // SCRUB: the compare-ending variant (scrub_kernels.hip): the same kernel up to the outputs, which
 // load the stored parity where the encode stores and compare (fetch / check); `sink` then carries
 // the lane's mismatch bits (bit x = parity node x) and nothing is written but a.res
+// BATCH: many stripes in one launch (stream_batch_kernels.hip): a tile carries its stripe
+// (StreamTile::stripe, BatchMap) and the nodes of stripe i are a.data[node] + i * a.sdata and
+// a.par[X] + i * a.spar.  The stripe is wave-uniform, so its offset goes into the SGPR base of every
+// access (stripe_off); the lanes' 32-bit offsets stay offsets in one chunk
 template <int KD, int LOADERS, int CPL = 0, int CPS = 0, bool CSE = true, bool SINK = false, bool CHECK = false,
-          int MAP = 0, bool LPRED = false, bool SCRUB = false>
+          int MAP = 0, bool LPRED = false, bool SCRUB = false, bool BATCH = false>
 struct StreamEnc {
     using K6 = EncMath<KD>;
     using S = typename K6::S;
@@ -170,6 +174,11 @@ struct StreamEnc {
     // parity stores (16-byte instructions) a lane issues at the end of group g (full tile)
     static constexpr int nstores(int g) { return 2 * (1 + 2 * g); }
     static constexpr int dshift(int y) { return 2 * (T - 2 - y); }  // digit y of the column c
+    // byte offset of tile t's stripe in a node family of stripe stride `stride` (BATCH; else 0)
+    __device__ __forceinline__ static int64_t stripe_off(StreamTile t, int64_t stride) {
+        if constexpr (BATCH) return int64_t(t.stripe) * stride;
+        return 0;
+    }
 
     // ---- node-buffer image ----
     // Row r (= column c, layer 4c + g) occupies bytes [256 r, 256 r + 256); its 16-byte
@@ -266,12 +275,12 @@ struct StreamEnc {
                 constexpr uint32_t b = (uint32_t(x) >> 1) & 1u;
                 const uint32_t dst = lds0 + uint32_t(node * NODE_BYTES) + uint32_t(L.li * BPL) * 1024u;
                 if (full) {
-                    const uint8_t *base = uniform_ptr(a.data[node] + (uint64_t(g) * sc + t.b0));
+                    const uint8_t *base = uniform_ptr(a.data[node] + stripe_off(t, a.sdata) + (uint64_t(g) * sc + t.b0));
 #pragma unroll
                     for (int j = 0; j < BPL; j++) dma16p<CPL>(dst + uint32_t(j) * 1024u, base, L.off[b][j]);
                 } else if (LPRED && ((t.vend - t.b0) & 15u) == 0) {
                     // piece 0 of every row lies inside the tile: no instruction is fully masked
-                    const uint8_t *base = uniform_ptr(a.data[node] + (uint64_t(g) * sc + t.b0));
+                    const uint8_t *base = uniform_ptr(a.data[node] + stripe_off(t, a.sdata) + (uint64_t(g) * sc + t.b0));
 #pragma unroll
                     for (int j = 0; j < BPL; j++) {
                         const uint64_t mask = __builtin_amdgcn_ballot_w64(k16_of(L, j, b) + 16u <= t.vend - t.b0);
@@ -280,7 +289,7 @@ struct StreamEnc {
                 } else {
                     // partial tile: a piece straddling vend is read from vend - 16 (patched
                     // after landing), a piece wholly past vend from b0 (never used)
-                    const uint8_t *base = uniform_ptr(a.data[node] + uint64_t(g) * sc);
+                    const uint8_t *base = uniform_ptr(a.data[node] + stripe_off(t, a.sdata) + uint64_t(g) * sc);
 #pragma unroll
                     for (int j = 0; j < BPL; j++) {
                         const uint32_t k16 = k16_of(L, j, b);
@@ -313,7 +322,8 @@ struct StreamEnc {
                     if (!(pos < t.vend && pos + 16u > t.vend)) continue;
                     const int blk = L.li * BPL + j;
                     const uint32_t layer = (uint32_t(blk) * 4u + L.rl) * 4u + uint32_t(g);
-                    const uint2 gv = *reinterpret_cast<const uint2 *>(a.data[node] + uint64_t(layer) * sc + pos);
+                    const uint2 gv =
+                        *reinterpret_cast<const uint2 *>(a.data[node] + stripe_off(t, a.sdata) + uint64_t(layer) * sc + pos);
                     *reinterpret_cast<uint4 *>(smem + node * NODE_BYTES + blk * 1024 + lane * 16) =
                         make_uint4(gv.x, gv.y, 0u, 0u);
                 }
@@ -562,7 +572,8 @@ struct StreamEnc {
                 pos = (l & 15u) << 4;  // part = lane bits 0-2, odd = bit 3
             }
             off += t.b0 + pos;
-            const uint8_t *base = uniform_ptr(a.par[X]);  // SGPR base (also under the probes' deferred flow)
+            // SGPR base (also under the probes' deferred flow)
+            const uint8_t *base = uniform_ptr(a.par[X] + stripe_off(t, a.spar));
             // A tile narrower than 256 (width a multiple of 16): lanes whose piece lies past vend
             // sit the two stores out.  Piece 0 of every row is inside every tile, so part 0 of the
             // even columns is active in every wave: both instructions always issue (the counted
@@ -579,7 +590,7 @@ struct StreamEnc {
             st16sp<CPS>(base, off, lo[0], lo[1], lo[2], lo[3]);
             st16sp<CPS>(base, off + PAIR * uint32_t(a.sc), hi[0], hi[1], hi[2], hi[3]);
         } else {
-            uint8_t *p = a.par[X] + uint64_t(z) * a.sc + t.b0 + prel;
+            uint8_t *p = a.par[X] + stripe_off(t, a.spar) + uint64_t(z) * a.sc + t.b0 + prel;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const uint32_t pos = t.b0 + prel + 128u * uint32_t(h);
@@ -826,11 +837,20 @@ constexpr int kStreamEncMap = 8;
 // scrub_kernels.hip): data and parity are read-only, a compute wave that saw a mismatch ORs its
 // bits into a.res[0] after its last tile; loader waves and workgroups without a tile never touch
 // a.res.  Only with dedicated loader waves: the counted waits of LOADERS == 0 count parity stores.
-template <int KD, int LOADERS, int PROBE = 0, int MAP = 0, bool SCRUB = false>
+// BATCH: a.nstripes stripes in one launch (stream_batch_kernels.hip), stripe i's nodes at
+// a.data[node] + i * a.sdata and a.par[X] + i * a.spar.  a.nslots is then the workgroups per XCD
+// of ONE stripe's cut and a.ntiles the groups of that many workgroups per XCD (BatchMap,
+// stream_tile_map.hpp); grid = 8 * a.ntiles * a.nslots.  The step loop runs unchanged over the
+// workgroup's longer tile sequence: the prefetch of step s + 2 may fetch the first tile of the
+// workgroup's next stripe, and a ragged tile (which ends a stripe's sequence) may be followed by
+// another stripe's tile -- its steps wait for vmcnt(0) before patching, which covers the two
+// prefetched steps whichever stripe they belong to, and the steps after it count as after any tile.
+template <int KD, int LOADERS, int PROBE = 0, int MAP = 0, bool SCRUB = false, bool BATCH = false>
 __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_encode(BsArgs a) {
     static_assert(!SCRUB || (LOADERS > 0 && PROBE == 0), "the scrub variant: loader waves, no probe bits");
+    static_assert(!(BATCH && (SCRUB || PROBE || LOADERS != 4)), "the batch variant: the library's encode only");
     using Kn = StreamEnc<KD, LOADERS, (PROBE >> 6) & 3, (PROBE >> 8) & 3, ((PROBE >> 10) & 1) == 0, (PROBE & 262144) != 0,
-                         (PROBE & 524288) != 0, MAP, (PROBE & 4194304) != 0, SCRUB>;
+                         (PROBE & 524288) != 0, MAP, (PROBE & 4194304) != 0, SCRUB, BATCH>;
     uint32_t sink = 0;  // SINK probes; SCRUB: the lane's mismatch bits
     constexpr bool TM = (PROBE & 4096) != 0;
     using K6 = typename Kn::K6;
@@ -841,7 +861,8 @@ __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_enco
     // tile, which takes the plain-store path whole) for the same-box A/B against BalancedMap
     constexpr bool OLDMAP = (PROBE & (2048 | 2097152)) != 0;
     const auto tm = [&] {
-        if constexpr ((PROBE & 2048) != 0) return ChipMap(uint32_t(a.sc), blockIdx.x, gridDim.x);
+        if constexpr (BATCH) return BatchMap(uint32_t(a.sc), a.tiles_per_xcd, ns, a.ntiles, a.nstripes, xcd, slot);
+        else if constexpr ((PROBE & 2048) != 0) return ChipMap(uint32_t(a.sc), blockIdx.x, gridDim.x);
         else if constexpr (OLDMAP) return StreamMap(uint32_t(a.sc), a.tiles_per_xcd, ns, xcd, slot);
         else return BalancedMap(uint32_t(a.sc), a.tiles_per_xcd, ns, xcd, slot);
     }();

@@ -31,6 +31,7 @@ namespace bs {
 
 struct StreamTile {
     uint32_t b0, vend;  // positions [b0, b0 + 256) of every row, valid below vend
+    uint32_t stripe;    // BatchMap: the stripe the tile belongs to (the one-stripe maps leave it 0)
 };
 
 struct BalancedMap {
@@ -59,7 +60,44 @@ struct BalancedMap {
     CLAY_TILE_MAP_HD int ntile() const { return int(nt); }
     CLAY_TILE_MAP_HD StreamTile tile(int k, uint32_t slot, uint32_t ns) const {
         const uint32_t b0 = start(uint32_t(k), slot, ns), e = b0 + width(uint32_t(k));
-        return {b0, e < x1 ? e : x1};
+        return {b0, e < x1 ? e : x1, 0u};
+    }
+};
+
+// A batch of n_stripes stripes of one sub-chunk size in one launch (k_stream_encode BATCH).
+// Every stripe keeps exactly the one-stripe cut: its region, ns = nsS workgroups per XCD and
+// BalancedMap(sc, region, nsS, xcd, sub).  The per_xcd workgroups of an XCD form
+// G = min(max(1, per_xcd / nsS), n_stripes) groups of nsS (batch_groups); workgroup `slot` is
+// sub-slot slot % nsS of group j = slot / nsS, and slots from G * nsS on are not launched (grid =
+// 8 * G * nsS).  Group j runs the stripes j, j + G, j + 2G, ... one after the other, each through
+// the same BalancedMap: the workgroup's tile k is round k % nt of stripe j + (k / nt) * G, where
+// nt = BalancedMap::ntile() is the same for every stripe because sc is.  So two groups' stripe
+// counts differ by at most one, a workgroup's stripes ascend, and its tile sequence is the
+// concatenation of one-stripe sequences (the kernel's flat step counter runs over it unchanged).
+CLAY_TILE_MAP_HD inline uint32_t batch_groups(uint32_t per_xcd, uint32_t ns, uint32_t n_stripes) {
+    const uint32_t fit = per_xcd / ns > 1u ? per_xcd / ns : 1u;
+    return fit < n_stripes ? fit : n_stripes;
+}
+
+struct BatchMap {
+    BalancedMap one;  // the cut of every stripe, for this workgroup's sub-slot
+    uint32_t ns, sub, first, groups, count;
+    CLAY_TILE_MAP_HD BatchMap(uint32_t sc, uint32_t region, uint32_t ns_, uint32_t groups_, uint32_t n_stripes, uint32_t xcd,
+                              uint32_t slot)
+        : one(sc, region, ns_, xcd, slot % ns_), ns(ns_), sub(slot % ns_), first(slot / ns_), groups(groups_) {
+        // stripes first, first + G, ... below n_stripes; none for a slot at or past G * ns
+        count = first < groups && first < n_stripes ? (n_stripes - first + groups - 1u) / groups : 0u;
+    }
+    CLAY_TILE_MAP_HD int stripes() const { return int(count); }
+    CLAY_TILE_MAP_HD int ntile() const { return one.ntile() * int(count); }
+    // stripe of the workgroup's tile k
+    CLAY_TILE_MAP_HD uint32_t stripe(int k) const { return first + uint32_t(k) / one.nt * groups; }
+    // (slot and ns of the one-stripe maps' signature are not used: the map holds its own)
+    CLAY_TILE_MAP_HD StreamTile tile(int k, uint32_t, uint32_t) const {
+        const uint32_t i = uint32_t(k) / one.nt;
+        StreamTile t = one.tile(int(uint32_t(k) - i * one.nt), sub, ns);
+        t.stripe = first + i * groups;
+        return t;
     }
 };
 

@@ -138,7 +138,16 @@ int clay_encode_device(const clay_code_t *code, const uint8_t *const *data_chunk
                        void *stream, clay_error_t *err);
 
 /* Batched encode: `n_stripes` independent stripes, stripe s uses
- * data_chunks[s*k .. s*k+k) and parity_chunks[s*m .. s*m+m). */
+ * data_chunks[s*k .. s*k+k) and parity_chunks[s*m .. s*m+m).
+ * (10,4,13) and (9,4,12), 2 or more stripes whose chunks are rows of one buffer (one
+ * stride for all data chunks, one for all parity chunks), every chunk and both strides
+ * 8-byte aligned, sub-chunk a multiple of 8 and at least 16 bytes: ONE launch of the
+ * batched streaming kernel (clay_last_encode_path "stream-batch-k10m4-w256-l4" /
+ * "stream-batch-k9m4-w256-l4", clay_last_launch_count 1) under encode path auto for stripes
+ * of more than 4 MiB of data with sub-chunks up to 262,152 bytes, and under "stream"
+ * (variant 0 or 4) at any size.  It allocates nothing and uploads no pointer table, so it
+ * can be captured without a warm call.  Everything else runs as before: smaller stripes
+ * the staged batch, other layouts one launch per stripe. */
 int clay_encode_device_batch(const clay_code_t *code, const uint8_t *const *data_chunks,
                              uint8_t *const *parity_chunks, size_t n_stripes, size_t chunk_size,
                              int device, void *stream, clay_error_t *err);
@@ -163,7 +172,12 @@ int clay_encode_host_pipelined(const clay_code_t *code, const uint8_t *const *da
  * node j at parity + s*parity_stripe_stride + j*parity_node_stride (bytes; e.g. a
  * contiguous [n_stripes][k][chunk] buffer has node stride chunk, stripe stride k*chunk).
  * Same results as clay_encode_device_batch with the equivalent pointer arrays, with O(1)
- * host work per call.  Asynchronous on `stream`. */
+ * host work per call.  Asynchronous on `stream`.
+ * (10,4,13) and (9,4,12) with base pointers and all four strides 8-byte aligned and the
+ * sub-chunk a multiple of 8 (at least 16): 2 or more stripes are ONE launch of the batched
+ * streaming kernel ("stream-batch-k10m4-w256-l4" / "stream-batch-k9m4-w256-l4"), under auto
+ * for stripes of more than 4 MiB of data with sub-chunks up to 262,152 bytes and under
+ * "stream" (variant 0 or 4) at any size; see clay_encode_device_batch. */
 int clay_encode_device_strided(const clay_code_t *code, const uint8_t *data, int64_t data_node_stride,
                                int64_t data_stripe_stride, uint8_t *parity, int64_t parity_node_stride,
                                int64_t parity_stripe_stride, size_t n_stripes, size_t chunk_size, int device,

@@ -6,6 +6,8 @@ decode  read (n-e)*chunk + write (#erased data nodes)*chunk
 repair  read d*beta*sc + write chunk
 scrub   read n*chunk (ONLY=scrub; scrub10: the (10,4,13) 1 GiB leg alone; scrub_gate: the sweep behind
         auto's gate for the streaming scrub)
+ONLY=batch_stream: many (10,4,13) stripes above 4 MiB per call, the streaming batch against a
+per-stripe loop; batch_stream_gate: the sweep behind auto's upper gate for it.
 Prints one JSON object per configuration."""
 import json
 import os
@@ -414,6 +416,64 @@ def scrub_batch_cfg(k, m, d, stripe, n, loop_stripes):
             "stripe_data_GiBps": round(nl * k * chunk / (ms * 1e-3) / 2**30, 1)})
 
 
+def batch_stream_cfg(sc, n, k=10, m=4, d=13, gate=False):
+    """ONLY=batch_stream: n stripes of (10,4,13) above the staged batch's 4 MiB (sub-chunk sc, about
+    1 GiB of data per call) through clay_encode_device_strided under auto -- one launch of the
+    batched streaming kernel ("stream-batch-..."; a library without it runs its own loop of one
+    launch per stripe inside the call) -- and through a loop of per-stripe clay_encode_device calls
+    on the same buffers, samples alternated.  Per variant: median / min / spread (max - min) of the
+    samples per call of n stripes, and GiB/s of stripe data."""
+    c = ClayCode(k, m, d)
+    chunk = c.sub_chunk_no * sc
+    data = rnd(n * k, chunk, 21).view(n, k, chunk)
+    par = torch.empty((n, m, chunk), dtype=torch.uint8, device="cuda")
+    dls = [[data[s, i] for i in range(k)] for s in range(n)]
+    pls = [[par[s, j] for j in range(m)] for s in range(n)]
+
+    def batch():
+        # ONLY=batch_stream_gate: under "stream", which takes the batch at any eligible size,
+        # whatever auto's gate says
+        if gate:
+            clay_amd.set_encode_path("stream", 0)
+        c.encode_device_strided(data, par, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+        if gate:
+            clay_amd.set_encode_path("auto", 0)
+
+    def loop():
+        for s in range(n):
+            c.encode_device(dls[s], pls[s], chunk, 0, stream.cuda_stream)
+
+    fns, info = [batch, loop], []
+    for fn in fns:
+        fn()
+        torch.cuda.synchronize()
+        info.append((clay_amd.last_encode_path(), clay_amd.last_launch_count()))
+    ts = [[] for _ in fns]
+    for i in range(RUNS + 2):
+        for j, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fn()
+            e0.record(stream)
+            for _ in range(B2B):
+                fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if i >= 2:
+                ts[j].append(e0.elapsed_time(e1) / B2B)
+    out = {"config": f"encode ({k},{m},{d}) batch_stream {n} x {k * chunk / 2**20:.0f} MiB (sc {sc})",
+           "stripe_data_bytes": n * k * chunk}
+    for tag, t, (path, launches) in zip(("strided", "loop"), ts, info):
+        med = float(np.median(t))
+        out[tag] = {"path": path, "launches_per_call": launches if tag == "strided" else n * launches,
+                    "median_ms": round(med, 4), "min_ms": round(float(np.min(t)), 4),
+                    "spread_ms": round(float(np.max(t) - np.min(t)), 4),
+                    "stripe_data_GiBps": round(n * k * chunk / (med * 1e-3) / 2**30, 1)}
+    if gate:
+        # a win: the batch's median is below the loop's by more than the spread of the loop's samples
+        out["batch_wins"] = bool(out["loop"]["median_ms"] - out["strided"]["median_ms"] > out["loop"]["spread_ms"])
+    print(json.dumps(out), flush=True)
+
+
 def repair_cfg(k, m, d, chunk, lost):
     c = ClayCode(k, m, d)
     sc = chunk // c.sub_chunk_no
@@ -455,6 +515,14 @@ if __name__ == "__main__":
             ("encode", lambda: encode_cfg(9, 3, 11, 9 * (256 << 20))),
             ("batch", lambda: encode_batch_cfg(4, 2, 5, 1 << 20, 256)),
             # the clay_bench.rs stripe sizes with node 0 lost in every stripe, ~64 MiB per call
+            # ONLY=batch_stream: many (10,4,13) stripes above 4 MiB, about 1 GiB of data per call, and
+            # two stripes of the benchmark's sub-chunk (DESIGN.md 4.4 "Streaming batches")
+            *[("batch_stream", (lambda a=a: batch_stream_cfg(*a))) for a in
+              ((2048, 205), (6560, 64), (26216, 16), (66176, 6), (419432, 2))],
+            # ONLY=batch_stream_gate: the sweep behind auto's gate for the streaming batch where one
+            # stripe already fills the chip (one group: only the launch seams are saved)
+            *[("batch_stream_gate", (lambda sc=sc, n=n: batch_stream_cfg(sc, n, gate=True)))
+              for sc in (32776, 66176, 131080, 262152, 419432) for n in (2, 3, 4, 6)],
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 1 << 10, 65536, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 10 << 10, 6553, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 100 << 10, 655, 0, 655)),
