@@ -8,13 +8,21 @@ independent codeword, so where one data byte is flipped in a large stripe the or
 the parity of the column pair holding the flip only; the other columns are the clean codeword's.
 
 What each sub-chunk size exercises in the kernel is asserted in test_scrub_stream_shapes_cpu.py.
+
+test_every_parity_byte_stream flips stored parity bytes one at a time (schedules: scrub_sweeps.py,
+checked in test_scrub_coverage_cpu.py): every byte at sc = 16, 24 and 264, the lane classes and
+tile edges at the larger sizes.  Every case prints its wall time (-s); the slowest measured on an
+MI355X: 1.09 s (66176-tile-edges, 14,688 calls at 74 us), 0.75 s for each of the 16 cases at 264
+(16,896 calls at 44 us), 0.73 s for 2288-rows (18,304 calls at 40 us).
 """
 import numpy as np
 import pytest
 
 import clay_amd
+import scrub_sweeps as sw
 from clay_amd import ClayCode
 from test_gpu_scrub import Stripes, _codeword, _expected, _oracle_parity, _places
+from test_scrub_stream_shapes_cpu import dump_tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -163,6 +171,31 @@ def test_capture_replay_stream(oracle_mod, torch_cuda):
                 st.flip(0, c.k + j, at, 0xFF)
         del g
         torch.cuda.synchronize()
+    finally:
+        clay_amd.set_exec_mode(prev)
+
+
+@pytest.fixture(scope="module")
+def sweep_tiles(tmp_path_factory):
+    """sc -> the tiles of the streaming kernel (stream_tile_dump, as test_scrub_stream_shapes_cpu.py)."""
+    return dump_tiles(tmp_path_factory.mktemp("sweep_tiles"), sorted({case[0] for case in sw.stream_cases()}))
+
+
+@pytest.mark.parametrize("case", sw.stream_cases(), ids=sw.case_id)
+def test_every_parity_byte_stream(torch_cuda, codewords, sweep_tiles, case):
+    """Every flip of the case (scrub_sweeps.stream_flips: the full product at 16, 24 and 264; at
+    1064 and 2288 every byte of eight layers and every layer at the tile edges and the ragged
+    tile's 16-byte boundaries; at 66176 and 66184 the tile edges in one layer per group) alone in
+    the stored parity: the mask is exactly 1 << j.  One clay_scrub_device call per flip into its
+    own result word, one synchronise at the end."""
+    c = ClayCode(*CFG)
+    sc = case[0]
+    cw = codewords(sc)
+    st = Stripes(torch_cuda, c, [cw], seed=sc)
+    jj, at = sw.stream_flips(case, sweep_tiles[sc])
+    prev = clay_amd.set_exec_mode("stream")
+    try:
+        sw.run_flip_loop(torch_cuda, clay_amd, st, jj, at, cw[c.k:], "stream-scrub", "stream sweep " + sw.case_id(case))
     finally:
         clay_amd.set_exec_mode(prev)
 

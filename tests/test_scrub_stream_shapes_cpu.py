@@ -32,21 +32,27 @@ def _launch_shape(sc):
     return region, min(PER_XCD, max(1, (region + 255) // 256))
 
 
-@pytest.fixture(scope="module")
-def tiles(tmp_path_factory):
-    """sc -> list of (xcd, slot, round, b0, vend)"""
-    exe = str(tmp_path_factory.mktemp("tiles") / "stream_tile_dump")
+def dump_tiles(workdir, sizes):
+    """sc -> list of (xcd, slot, round, b0, vend): stream_tile_dump compiled into `workdir` and run
+    on `sizes` (also the tile boundaries of the flip sweeps, tests/scrub_sweeps.py)."""
+    exe = os.path.join(str(workdir), "stream_tile_dump")
     subprocess.run([_compiler(), "-std=c++17", "-O2", "-Wall", "-Werror", "-I", INC, "-o", exe, SRC], check=True)
     args = []
-    for sc in SIZES:
+    for sc in sizes:
         args += [str(sc), *map(str, _launch_shape(sc))]
     r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, check=True)
-    out = {sc: [] for sc in SIZES}
+    out = {sc: [] for sc in sizes}
     for line in r.stdout.split("\n"):
         if line:
             sc, *t = map(int, line.split())
             out[sc].append(tuple(t))
     return out
+
+
+@pytest.fixture(scope="module")
+def tiles(tmp_path_factory):
+    """sc -> list of (xcd, slot, round, b0, vend)"""
+    return dump_tiles(tmp_path_factory.mktemp("tiles"), SIZES)
 
 
 def _widths(ts, xcd=None, rnd=None):
