@@ -28,6 +28,7 @@ __all__ = [
     "InsufficientHelperData", "InconsistentChunkSizes", "TooManyErasures",
     "ReconstructionFailed", "MissingYSectionHelper", "Overflow", "DeviceError",
     "set_encode_path", "last_encode_path", "last_launch_count", "set_exec_mode", "last_exec_path",
+    "set_scrub_path",
 ]
 
 
@@ -132,11 +133,38 @@ def set_exec_mode(mode: str) -> str:
     least 16 bytes, every chunk 8-byte aligned) runs the streaming kernel ('stream-scrub') under
     'stream' at any size and under 'auto', 'stream-local' and 'stream-fused2' from a sub-chunk of
     65,536 bytes up; 'grouped' / 'tile' keep v1 ('bs-scrub'), and so does every stripe off 8-byte
-    rows.  Every other scrub is the same in all modes.  Returns the previous mode."""
+    rows.  Batches of such stripes at uniform strides run in one launch ('stream-scrub-batch') as
+    set_scrub_path says: under 'stream' only with scrub path 'stream-batch' (else one launch per
+    stripe), under 'auto', 'stream-local' and 'stream-fused2' also by auto's gate, never under
+    'grouped' / 'tile'.  Every other scrub is the same in all modes.  Returns the previous mode."""
     if mode not in _EXEC_MODES:
         raise ValueError(f"unknown exec mode {mode!r}")
     prev = _lib.lib().clay_set_exec_mode(_EXEC_MODES[mode])
     return {v: k for k, v in _EXEC_MODES.items()}[prev]
+
+
+_SCRUB_PATHS = {"auto": 0, "stream-batch": 1}
+
+
+def set_scrub_path(name: str) -> str:
+    """Process-wide path of the batched scrubs of (10,4,13) (scrub_device_batch / _strided):
+    'auto' | 'stream-batch'.  An eligible call -- 2 or more stripes, every stripe on 8-byte rows
+    (see set_exec_mode), one data and one parity stripe stride (a data stride of 0 included), exec
+    mode not 'grouped' / 'tile' -- can run as ONE launch of the streaming kernel's batch variant
+    (last_exec_path 'stream-scrub-batch', last_launch_count 1).  'stream-batch' takes it for every
+    eligible call, at any sub-chunk size from 16 bytes, under exec modes 'auto', 'stream',
+    'stream-local' and 'stream-fused2'; 'auto' (the default) takes it by the measured gate of
+    clay.h (sub-chunks of 2,048 to 66,176 bytes whose batch gives every XCD at least 20 full
+    256-byte tiles, e.g. 20 stripes at 2,048 or 2 from 20,480), never under exec mode 'stream'
+    (one launch per stripe, the A/B partner).  The path only chooses kernels: the result words are
+    the same.
+    Anything else raises ValueError and changes nothing.  Returns the previous path name."""
+    if name not in _SCRUB_PATHS:
+        raise ValueError(f"unknown scrub path {name!r}")
+    prev = _lib.lib().clay_set_scrub_path(_SCRUB_PATHS[name])
+    if prev < 0:
+        raise ValueError(f"unknown scrub path {name!r}")
+    return {v: k for k, v in _SCRUB_PATHS.items()}[prev]
 
 
 def last_exec_path() -> str:
@@ -144,8 +172,9 @@ def last_exec_path() -> str:
     'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
     'bs-decode1-batch' (the batched decodes) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
     (both) | the scrubs' 'bs-scrub1' / 'bs-scrub' (one launch per stripe), 'bs-scrub1-batch' /
-    'bs-scrub-batch' (a batch in one launch) and 'stream-scrub' ((10,4,13) on the streaming kernel:
-    one launch per stripe in every entry point) | 'none'."""
+    'bs-scrub-batch' (a batch in one launch), 'stream-scrub' ((10,4,13) on the streaming kernel:
+    one launch per stripe in every entry point) and 'stream-scrub-batch' (many stripes in one
+    launch of that kernel, see set_scrub_path) | 'none'."""
     return _lib.lib().clay_last_exec_path().decode()
 
 
@@ -348,8 +377,10 @@ class ClayCode:
         data_chunks[s*k .. s*k+k) and parity_chunks[s*m .. s*m+m); result: n_stripes uint32 in
         device memory, one mask per stripe.  One launch where the stripes sit at uniform strides
         (last_exec_path 'bs-scrub1-batch' / 'bs-scrub-batch'), else one per stripe.  (10,4,13) on
-        the streaming kernel ('stream-scrub', see set_exec_mode; every stripe of the call must be
-        on 8-byte rows) is one launch per stripe: last_launch_count() == n_stripes."""
+        the streaming kernel (see set_exec_mode; every stripe of the call must be on 8-byte rows):
+        2 or more stripes at uniform strides in ONE launch ('stream-scrub-batch') where
+        set_scrub_path says so, else one launch per stripe ('stream-scrub', last_launch_count() ==
+        n_stripes)."""
         dp = (C.c_void_p * max(1, self.k * n_stripes))(*[_ptr(x) for x in data_chunks])
         pp = (C.c_void_p * max(1, self.m * n_stripes))(*[_ptr(x) for x in parity_chunks])
         err = ClayErrorStruct()
@@ -365,8 +396,9 @@ class ClayCode:
         """Scrub stripes at fixed strides in one launch (clay.h clay_scrub_device_strided).
         Strides default to a contiguous [n_stripes][k or m][chunk_size] layout; result:
         n_stripes uint32 in device memory.  Allocates nothing: capturable unprepared.  (10,4,13)
-        on the streaming kernel ('stream-scrub', see set_exec_mode; base and strides multiples of
-        8) is one launch per stripe."""
+        on the streaming kernel (see set_exec_mode; base and strides multiples of 8) is one launch
+        too where set_scrub_path says so ('stream-scrub-batch'), else one launch per stripe
+        ('stream-scrub')."""
         dns = data_node_stride or chunk_size
         dss = data_stripe_stride or self.k * chunk_size
         pns = parity_node_stride or chunk_size

@@ -1805,11 +1805,34 @@ hipError_t launch_stream_batch_kernel(int kd, const bs::BsArgs &a, hipStream_t s
 // no pointer table: stripe 0's pointers and the two strides travel in the kernel arguments.
 // Anything it does not take (a chunk off the stride, rows off 8-byte alignment, odd sc) leaves
 // *done false and the caller goes on as before.
+// The launch geometry of k_stream_encode BATCH, for the batched encode and the batched scrub:
+// one stripe's cut as launch_stream (region, nslots workgroups per XCD) and G groups of nslots
+// workgroups per XCD, into a.sc / tiles_per_xcd / nslots / ntiles / nstripes.  false: the kernel
+// cannot take the batch (fewer than 2 stripes, more than its 32-bit stripe index holds, or more
+// steps for one workgroup than its int step counter)
+static bool stream_batch_geometry(const DevProps &prop, size_t ns, size_t sc, bs::BsArgs &a) {
+    if (ns < 2 || ns > 0xFFFFFFFFull) return false;
+    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
+    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
+    const uint32_t nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
+    const uint32_t groups = bs::batch_groups(per_xcd, nslots, uint32_t(ns));
+    // a workgroup's steps (12 per tile) are counted in an int: rounds per stripe x stripes per group
+    const uint64_t rounds = (uint64_t(region) + uint64_t(nslots) * 256u - 1u) / (uint64_t(nslots) * 256u);
+    if (rounds * ((ns + groups - 1) / groups) * 12u > 0x7FFFFFFFull) return false;
+    a.sc = sc;
+    a.tiles_per_xcd = region;
+    a.nslots = nslots;
+    a.ntiles = groups;
+    a.nstripes = uint32_t(ns);
+    return true;
+}
+
 template <int KD>
 static Error launch_stream_batch(CodeState &cs, const DevProps &prop, const StripeOperands &data, const StripeOperands &par,
                                  size_t ns, size_t sc, hipStream_t stream, bool *done) {
     using Kn = bs::StreamEnc<KD, 4>;
     using S = typename Kn::S;
+    static_assert(Kn::STEPS == 12, "stream_batch_geometry counts 12 steps per tile");
     // 8-byte rows, a clamped 16-byte piece, 32-bit chunk offsets in the lanes
     if (sc % 8 != 0 || sc < 16 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
     if (ns < 2 || ns > 0xFFFFFFFFull) return Error{};
@@ -1822,22 +1845,10 @@ static Error launch_stream_batch(CodeState &cs, const DevProps &prop, const Stri
     par.stripe_ptrs(0, p0);
     if (misaligned8(d0, size_t(KD), sdata) || misaligned8(p0, 4, spar)) return Error{};
     if (Error e = rs_matches<S, 4>(cs)) return e;
-    // one stripe's cut, as launch_stream; G groups of nslots workgroups per XCD
-    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
-    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
-    const uint32_t nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
-    const uint32_t groups = bs::batch_groups(per_xcd, nslots, uint32_t(ns));
-    // a workgroup's steps (12 per tile) are counted in an int: rounds per stripe x stripes per group
-    const uint64_t rounds = (uint64_t(region) + uint64_t(nslots) * 256u - 1u) / (uint64_t(nslots) * 256u);
-    if (rounds * ((ns + groups - 1) / groups) * uint64_t(Kn::STEPS) > 0x7FFFFFFFull) return Error{};
     bs::BsArgs a{};
+    if (!stream_batch_geometry(prop, ns, sc, a)) return Error{};
     for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? d0[i] : nullptr;
     for (int x = 0; x < 4; x++) a.par[x] = p0[x];
-    a.sc = sc;
-    a.tiles_per_xcd = region;
-    a.nslots = nslots;
-    a.ntiles = groups;
-    a.nstripes = uint32_t(ns);
     a.sdata = sdata;
     a.spar = spar;
     CLAY_HIP(launch_stream_batch_kernel(KD, a, stream, prop.dev));
@@ -2042,6 +2053,31 @@ static Error launch_stream_scrub(CodeState &cs, const DevProps &prop, uint8_t *c
     return Error{};
 }
 
+// ns >= 2 stripes of (10,4,13) in ONE launch of the compare-ending k_stream_encode BATCH
+// (scrub_kernels.hip): the batched encode's geometry (`a` from stream_batch_geometry), stripe 0's
+// pointers and the two strides in the kernel arguments, res[s] the word of stripe s.  No allocation
+// and no pointer table, so a first call inside a stream capture works.  The caller has checked the
+// shape of every stripe (stream_scrub_ok) and the strides (uniform_stride)
+static Error launch_stream_scrub_batch(CodeState &cs, const DevProps &prop, bs::BsArgs a, uint8_t *const *data0,
+                                       uint8_t *const *par0, int64_t sdata, int64_t spar, uint32_t *res,
+                                       hipStream_t stream) {
+    using S = typename bs::StreamEnc<10, 4>::S;
+    if (Error e = rs_matches<S, 4>(cs)) return e;
+    for (int i = 0; i < S::K; i++) a.data[i] = i < 10 ? data0[i] : nullptr;
+    for (int x = 0; x < 4; x++) a.par[x] = par0[x];
+    a.sdata = sdata;
+    a.spar = spar;
+    a.res = res;
+    CLAY_HIP(launch_stream_scrub_batch_kernel(a, stream, prop.dev));
+    t_last_launches++;
+    return Error{};
+}
+
+// Scrub path selection (clay_set_scrub_path): process-wide, read without locks.  Like the exec
+// modes it only chooses kernels: every value gives the same result words.
+enum : int { kScrubPathAuto = 0, kScrubPathStreamBatch = 1 };
+static std::atomic<int> g_scrub_path{kScrubPathAuto};
+
 // Auto's gate for the streaming scrub: the smallest sub-chunk from which it beat the v1 scrub at
 // that size and every larger one of the sweep (scripts/bench_paths.py ONLY=scrub_gate, DESIGN.md
 // 4.13, profiles/r11/scrub_stream.txt): 44.5 vs 68.6 us at 65,536, 92 vs 201 us at 131,072,
@@ -2064,6 +2100,35 @@ static bool stream_scrub_ok(const clay_code_t &c, const StripeOperands &data, co
         return !misaligned8(f.ptrs, n_stripes * f.per);
     };
     return rows8(data) && rows8(par);
+}
+
+// Auto's gate for the streaming batch of the scrub (scrub path auto, exec modes auto, "stream-local"
+// and "stream-fused2"), measured against the path the call takes without it -- below
+// kScrubStreamMinSc one launch of v1 ("bs-scrub-batch"), from it up the per-stripe "stream-scrub"
+// loop (scripts/bench_paths.py ONLY=scrub_batch_gate and scrub_batch_fill, DESIGN.md 4.13,
+// profiles/r13/scrub_stream_batch.txt; a win: the batch's median below the partner's by more than
+// the spread of the partner's samples).  Every swept point the gate admits is a win.
+//  * kScrubBatchMinSc: one full 256-byte tile per XCD; below it the tile is mostly empty (not swept).
+//  * kScrubBatchMinFill: the batch has a floor of 38-50 us (12 barriered steps per tile) that v1
+//    does not have, so it needs work for most of the chip: min(G, n) groups per XCD times the XCD's
+//    region, in 256-byte tiles.  16 tiles per XCD lose at every size (4,096 x 8: 41.7 vs 38.6 us;
+//    8,192 x 4: 40.6 vs 39.0; 16,384 x 2: 42.0 vs 38.4), 20 and more win (2,048 x 20: 44.1 vs 52.5;
+//    8,216 x 5: 50.4 vs 57.4; 2,048 x 32: 49.4 vs 70.3; 32,768 x 2: 47.5 vs 72.2), and deeper batches
+//    by 2.0-2.3x (8,192 x 51, 1 GiB: 295 vs 605 us).
+//  * kScrubBatchMaxSc: against the loop the batch only saves the seams between launches.  It wins
+//    for 2, 3, 4 and 6 stripes at 65,536 (2: 90.7 vs 97.6 us; 6: 247 vs 292) and 66,176 (6: 422 vs
+//    445); at 131,080 two stripes tie within the spread (237.2 vs 241.0, spread 5.0) while 3 to 6
+//    win by 3-4 %, at 262,152 all win by 2-3 %, at 419,432 all tie.  No bound on sc and fill
+//    separates 131,080 x 2 from its neighbours, so above 66,176 auto keeps the loop.
+constexpr size_t kScrubBatchMinSc = 2048;
+constexpr size_t kScrubBatchMaxSc = 66176;
+constexpr uint64_t kScrubBatchMinFill = 20;  // 256-byte tiles per XCD over the groups' first stripes
+
+// `a`: the batch's geometry (stream_batch_geometry: a.ntiles = min(G, n) groups, a.tiles_per_xcd =
+// the XCD's region in bytes)
+static bool scrub_stream_batch_auto(size_t sc, const bs::BsArgs &a) {
+    return sc >= kScrubBatchMinSc && sc <= kScrubBatchMaxSc &&
+           uint64_t(a.ntiles) * a.tiles_per_xcd >= kScrubBatchMinFill * 256u;
 }
 
 // data / par: as encode_device_impl's, both read-only here.  result: n_stripes device words, every
@@ -2110,8 +2175,21 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
     // (10,4,13) on 8-byte rows: the streaming kernel, under "stream" at any size, under auto and the
     // other streaming modes from kScrubStreamMinSc up; "grouped" / "tile" keep v1, its A/B partner.
     // One path per call: every stripe of the call is eligible, or none takes it
-    const bool streamed = xm != kExecGrouped && xm != kExecTile && (xm == kExecStream || sc >= kScrubStreamMinSc) &&
-                          stream_scrub_ok(c, data, par, n_stripes, sc);
+    const bool stream_shape = xm != kExecGrouped && xm != kExecTile && stream_scrub_ok(c, data, par, n_stripes, sc);
+    const bool streamed = stream_shape && (xm == kExecStream || sc >= kScrubStreamMinSc);
+    // ... and several stripes of it at one data and one parity stride (a data stride of 0, every
+    // stripe on the same data chunks, included: data is read-only) in ONE launch of that kernel's
+    // batch variant: wherever eligible under scrub path "stream-batch", by the measured gate under
+    // scrub path auto -- except exec mode "stream", which stays the per-stripe loop, the batch's A/B
+    // partner.  A call that is not eligible goes on exactly as without the batch
+    bs::BsArgs batch_args{};
+    int64_t bsdata = 0, bspar = 0;
+    const bool want_batch =
+        stream_shape && stream_batch_geometry(prop, n_stripes, sc, batch_args) &&  // 2 stripes or more
+        (g_scrub_path.load(std::memory_order_relaxed) == kScrubPathStreamBatch ||
+         (xm != kExecStream && scrub_stream_batch_auto(sc, batch_args)));
+    const bool batched = want_batch && uniform_stride(data, 0, n_stripes, nullptr, c.k, &bsdata) &&
+                         uniform_stride(par, 0, n_stripes, nullptr, c.m, &bspar);
     auto launch = [&](uint8_t *const *d0, uint8_t *const *p0, int64_t sdata, int64_t spar, size_t ns, uint32_t *res,
                       bool *done) {
         if (line) return launch_bs_scrub1(cs, prop, d0, p0, sdata, spar, ns, sc, res, st, done);
@@ -2144,8 +2222,16 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
         }
     }
     std::vector<uint8_t *> d0(c.k), p0(c.m);
+    if (batched) {
+        data.stripe_ptrs(0, d0.data());
+        par.stripe_ptrs(0, p0.data());
+        e = launch_stream_scrub_batch(cs, prop, batch_args, d0.data(), p0.data(), bsdata, bspar, result, st);
+        if (e) return e;
+        t_last_exec = "stream-scrub-batch";
+        return Error{};
+    }
     if (streamed) {
-        // one launch per stripe in every entry point (no one-launch batch on this kernel)
+        // one launch per stripe (exec mode "stream", or a call the batch variant does not take)
         for (size_t s = 0; s < n_stripes; s++) {
             data.stripe_ptrs(s, d0.data());
             par.stripe_ptrs(s, p0.data());
@@ -3219,6 +3305,10 @@ int clay_set_exec_mode(int mode) {
         mode != kExecStreamLocal && mode != kExecStreamFused2)
         return -1;
     return g_exec_mode.exchange(mode);
+}
+int clay_set_scrub_path(int path) {
+    if (path != kScrubPathAuto && path != kScrubPathStreamBatch) return -1;
+    return g_scrub_path.exchange(path);
 }
 const char *clay_last_encode_path(void) { return t_last_path.c_str(); }
 const char *clay_last_exec_path(void) { return t_last_exec; }

@@ -19,6 +19,13 @@ hipError_t launch_bs_scrub_kernel(int k, int m, bool bt, const bs::BsArgs &a, hi
 // set; rows 8-byte aligned, a.sc % 8 == 0, a.sc >= 16, 256 * a.sc < 2^32.  Sets the kernel's
 // dynamic-LDS attribute once per device `dev`
 hipError_t launch_stream_scrub_kernel(const bs::BsArgs &a, hipStream_t stream, int dev);
+// scrub_kernels.hip: k_stream_encode<10, 4 loaders, .., SCRUB, BATCH>: a.nstripes stripes of
+// (10,4,13) in one launch, stripe i's nodes at a.data[node] + i * a.sdata and a.par[X] + i * a.spar,
+// its result word a.res[i].  The batched streaming encode's arguments (a.nslots = workgroups per
+// XCD of one stripe's cut, a.ntiles = groups of them; grid 8 * a.ntiles * a.nslots) with a.res set;
+// the one-stripe launcher's conditions hold for every stripe.  Sets the dynamic-LDS attribute once
+// per device `dev`
+hipError_t launch_stream_scrub_batch_kernel(const bs::BsArgs &a, hipStream_t stream, int dev);
 
 // The one column-group count (PG) per code the v1 scrub is instantiated with: the host sizes
 // tiles and slots from BsKernel<KD, M, ScrubPg<KD, M>::value>

@@ -3,7 +3,8 @@
 // (bitslice.hpp, v1) for (4,2), (6,3), (8,4), (9,3) and (10,4) with d = n - 1, each with and
 // without byte tails.  Same kernels as the encodes up to the last step, which loads the stored
 // parity and compares where the encode stores.  And the compare-ending variant of the streaming
-// encode k_stream_encode (stream_encode.hpp) for (10,4,13).
+// encode k_stream_encode (stream_encode.hpp) for (10,4,13), one stripe per launch and, with the
+// batched tile map (BATCH), many stripes in one.
 #include <mutex>
 #include <set>
 
@@ -62,6 +63,26 @@ hipError_t launch_stream_scrub_kernel(const bs::BsArgs &a, hipStream_t stream, i
         }
     }
     kern<<<dim3(a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
+    return hipGetLastError();
+}
+
+// The same kernel over many stripes in one launch (SCRUB && BATCH: BatchMap, a.ntiles groups of
+// a.nslots workgroups per XCD, one result word per stripe).
+hipError_t launch_stream_scrub_batch_kernel(const bs::BsArgs &a, hipStream_t stream, int dev) {
+    using Kn = bs::StreamEnc<10, 4>;
+    constexpr auto kern = &bs::k_stream_encode<10, 4, 0, bs::kStreamEncMap, true, true>;
+    static std::mutex mu;
+    static std::set<int> done;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!done.count(dev)) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
+            if (e != hipSuccess) return e;
+            done.insert(dev);
+        }
+    }
+    kern<<<dim3(8 * a.ntiles * a.nslots), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();
 }
 

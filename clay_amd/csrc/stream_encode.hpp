@@ -651,7 +651,8 @@ struct StreamEnc {
         const uint32_t pos = pair_pos(prel, odd);
         off += t.b0 + pos;
         const uint64_t mask = __builtin_amdgcn_ballot_w64(!ragged && pos + 16u <= t.vend - t.b0);
-        ld16s2_masked(s.lo, s.hi, uniform_ptr(a.par[X]), off, off + PAIR * uint32_t(a.sc), mask);
+        // SGPR base with the stripe's offset, as put<X>'s
+        ld16s2_masked(s.lo, s.hi, uniform_ptr(a.par[X] + stripe_off(t, a.spar)), off, off + PAIR * uint32_t(a.sc), mask);
         return s;
     }
     template <int X, int AFTER>
@@ -671,7 +672,7 @@ struct StreamEnc {
         if (ragged) {
             // the bytes the encode stores plainly: 16 when nv == 16, 8 when nv >= 8, nothing otherwise
             x = 0;
-            const uint8_t *p = a.par[X] + uint64_t(z) * a.sc + t.b0 + prel;
+            const uint8_t *p = a.par[X] + stripe_off(t, a.spar) + uint64_t(z) * a.sc + t.b0 + prel;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const uint32_t pos = t.b0 + prel + 128u * uint32_t(h);
@@ -845,10 +846,19 @@ constexpr int kStreamEncMap = 8;
 // workgroup's next stripe, and a ragged tile (which ends a stripe's sequence) may be followed by
 // another stripe's tile -- its steps wait for vmcnt(0) before patching, which covers the two
 // prefetched steps whichever stripe they belong to, and the steps after it count as after any tile.
+// SCRUB && BATCH (scrub_kernels.hip): the stored parity of stripe i is read at a.par[X] + i * a.spar
+// (fetch / check, in the SGPR base as put's), and a compute wave reports after the group-3 end of the
+// last tile of each stripe's sequence ((k + 1) % nt == 0) into a.res[stripe], then starts the next
+// stripe with sink = 0; nothing is reported after the loop.  The loader waves' waits are the
+// encode's, argued above: the compare side adds no VMEM to them.  A compute wave's own loads never
+// cross a group end: every end_group closes with check<G, 0> (vmcnt(0)) and the ragged tile's plain
+// loads are waited for by the compiler, so a stripe's first fetch starts with nothing of the wave's
+// in flight but, at most, the report's atomic -- older than every load counted behind it, so the
+// counted waits only cover more.
 template <int KD, int LOADERS, int PROBE = 0, int MAP = 0, bool SCRUB = false, bool BATCH = false>
 __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_encode(BsArgs a) {
     static_assert(!SCRUB || (LOADERS > 0 && PROBE == 0), "the scrub variant: loader waves, no probe bits");
-    static_assert(!(BATCH && (SCRUB || PROBE || LOADERS != 4)), "the batch variant: the library's encode only");
+    static_assert(!(BATCH && (PROBE || LOADERS != 4)), "the batch variant: the library's encode and scrub only");
     using Kn = StreamEnc<KD, LOADERS, (PROBE >> 6) & 3, (PROBE >> 8) & 3, ((PROBE >> 10) & 1) == 0, (PROBE & 262144) != 0,
                          (PROBE & 524288) != 0, MAP, (PROBE & 4194304) != 0, SCRUB, BATCH>;
     uint32_t sink = 0;  // SINK probes; SCRUB: the lane's mismatch bits
@@ -1052,6 +1062,14 @@ __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_enco
             } else {
                 end_any(ge, t);
             }
+            if constexpr (SCRUB && BATCH) {
+                // the last tile of a stripe's sequence is done (k and the stripe are wave-uniform, every
+                // lane of the compute wave is here): report into the stripe's word, start the next clean
+                if (g == Kn::Q - 1 && uint32_t(k + 1) % tm.one.nt == 0) {
+                    scrub_report<4>(a.res + t.stripe, sink);
+                    sink = 0;
+                }
+            }
             st2 = st1;
             st1 = ragged ? 0 : Kn::nstores(ge);  // a ragged tile's plain stores are not counted:
                                                  // the waits then cover more than needed
@@ -1064,7 +1082,8 @@ __global__ __launch_bounds__((StreamEnc<KD, LOADERS>::BLOCK)) void k_stream_enco
     if constexpr (DEFER) {
         if (pend >= 0) end_any(pend, pt);
     }
-    if constexpr (SCRUB) scrub_report<4>(a.res, sink);  // every compute wave, in uniform control flow
+    // every compute wave, in uniform control flow (BATCH: reported per stripe in the step loop)
+    if constexpr (SCRUB && !BATCH) scrub_report<4>(a.res, sink);
     if constexpr ((PROBE & 262144) != 0) {
         // a.sdata is 0 in the probe: the predicate is (almost) never true, but not foldable
         if (sink == uint32_t(a.sdata) + 0x9E3779B9u) a.par[0][threadIdx.x] = uint8_t(sink);

@@ -219,9 +219,18 @@ int clay_scrub_device(const clay_code_t *code, const uint8_t *const *data_chunks
  * path "bs-scrub1-batch" / "bs-scrub-batch"); any other arrangement takes one launch per
  * stripe ("bs-scrub1" / "bs-scrub", clay_last_launch_count = n_stripes).  (10,4,13) on the
  * streaming kernel (see clay_scrub_device; EVERY stripe of the call must be on 8-byte rows,
- * else none takes it: one path per call) has no one-launch batch: "stream-scrub" is one launch
- * per stripe in the batch and strided forms too, clay_last_launch_count = n_stripes.
- * n_stripes = 0 returns CLAY_OK and touches nothing. */
+ * else none takes it: one path per call): 2 or more stripes at one data and one parity stripe
+ * stride (a data stride of 0 included) can run in ONE launch of its batch variant, last exec path
+ * "stream-scrub-batch", clay_last_launch_count = 1 -- for every such call under
+ * clay_set_scrub_path(1); by default (scrub path 0 auto, exec modes 0 / 5 / 6) for sub-chunks of
+ * 2,048 to 66,176 bytes when the first stripes of the batch's workgroup groups give every XCD at
+ * least 20 full 256-byte tiles (min(G, n_stripes) x the XCD's share of a row >= 5,120 bytes, G =
+ * the groups of one stripe's workgroups an XCD holds; e.g. 20 stripes at 2,048, 5 at 8,192, 2 from
+ * 20,480): there it beat the path below in every measured case, 2.0-2.2x for 1 GiB of stripes of
+ * 5 to 80 MiB.  Every other call on the streaming kernel ("stream-scrub": exec
+ * mode 3 stream with scrub path auto, sub-chunks from 65,536 bytes outside the gate, stripes off
+ * the stride) is one launch per stripe in the batch and strided forms too, clay_last_launch_count
+ * = n_stripes.  n_stripes = 0 returns CLAY_OK and touches nothing. */
 int clay_scrub_device_batch(const clay_code_t *code, const uint8_t *const *data_chunks,
                             const uint8_t *const *parity_chunks, uint32_t *result, size_t n_stripes,
                             size_t chunk_size, int device, void *stream, clay_error_t *err);
@@ -229,9 +238,10 @@ int clay_scrub_device_batch(const clay_code_t *code, const uint8_t *const *data_
 /* Batched scrub of stripes at fixed strides, the layout of clay_encode_device_strided: data
  * node i of stripe s at data + s*data_stripe_stride + i*data_node_stride, parity node j at
  * parity + s*parity_stripe_stride + j*parity_node_stride.  One launch, O(1) host work --
- * except (10,4,13) on the streaming kernel ("stream-scrub": both bases and all four strides
- * multiples of 8), one launch per stripe.  Bytes between the chunks are never read into the
- * answer. */
+ * also for (10,4,13) on the streaming kernel's batch variant ("stream-scrub-batch": both bases
+ * and all four strides multiples of 8; see clay_scrub_device_batch and clay_set_scrub_path for
+ * when it is taken); "stream-scrub" is one launch per stripe.  Bytes between the chunks are never
+ * read into the answer. */
 int clay_scrub_device_strided(const clay_code_t *code, const uint8_t *data, int64_t data_node_stride,
                               int64_t data_stripe_stride, const uint8_t *parity, int64_t parity_node_stride,
                               int64_t parity_stripe_stride, uint32_t *result, size_t n_stripes,
@@ -476,7 +486,8 @@ int clay_set_encode_path(int mode);
  *    except under 1 grouped and 2 tile, which keep v1, "bs-scrub" / "bs-scrub-batch", its A/B
  *    partner; (10,4,13) on 8-byte rows on the streaming kernel, "stream-scrub", under 3 stream
  *    at any sub-chunk and under 0 auto / 5 / 6 from a sub-chunk of 65,536 bytes, v1 under 1 / 2;
- *    everything else on v1 in every mode)
+ *    batches of it in one launch, "stream-scrub-batch", as clay_set_scrub_path says -- never
+ *    under 1 / 2, and under 3 stream only with scrub path 1; everything else on v1 in every mode)
  *   3 stream  -- every decode a streaming kernel takes on it: the local decode where it takes
  *                the pattern (the (2,1) patterns: the fused decode v2 first), else the fused
  *                decode v2 (2-4 erasures, at most two per section); everything else as auto
@@ -494,6 +505,22 @@ int clay_set_encode_path(int mode);
  * once when the library is loaded.
  * Returns the previous mode, or -1 for an unknown mode (setting unchanged). */
 int clay_set_exec_mode(int mode);
+/* Path of the batched scrubs of (10,4,13), clay_scrub_device_batch / _strided (process-wide tuning
+ * knob, like the two above).  It only chooses kernels: every value gives the same result words.
+ * A call is ELIGIBLE for the streaming batch -- ONE launch of k_stream_encode's compare-ending
+ * batch variant for all its stripes, last exec path "stream-scrub-batch", clay_last_launch_count
+ * 1 -- when it has 2 or more stripes, every stripe is on 8-byte rows (clay_scrub_device), the
+ * stripes sit at one data and one parity stripe stride (a data stride of 0, every stripe on the
+ * same data chunks, included), the exec mode is not 1 grouped / 2 tile, and one workgroup's steps
+ * fit the kernel's 31-bit counter.  A call that is not eligible runs as without this setter.
+ *   0 auto         -- under exec mode 3 stream: never (one launch per stripe, "stream-scrub": the
+ *                     batch's A/B partner).  Under exec modes 0 auto, 5 and 6: the streaming batch
+ *                     by the measured gate (see clay_scrub_device_batch), never below a sub-chunk
+ *                     of 2,048 bytes; else as without this setter
+ *   1 stream-batch -- the streaming batch for every eligible call, at any sub-chunk size from 16
+ *                     bytes and any stripe count from 2, under exec modes 0, 3, 5 and 6
+ * Returns the previous value, or -1 for any other value (setting unchanged). */
+int clay_set_scrub_path(int path);
 /* Plan executor the calling thread's last decode / repair / staged encode ran on:
  * "tile" (k_texec), "grouped" (k_gexec), "stream-local256" (k_stream_local256), "stream-local"
  * (k_stream_local), "stream-fused2"
@@ -502,8 +529,9 @@ int clay_set_exec_mode(int mode);
  * stripes), the batched repairs' "bs-repair-batch" (k_bs_repair over many stripes), both batches'
  * "grouped-batch" (k_gexec over many stripes), the scrubs' "bs-scrub1" (k_bs_encode1's compare
  * ending) / "bs-scrub" (k_bs_encode's) with one launch per stripe and "bs-scrub1-batch" /
- * "bs-scrub-batch" (a batch in one launch) and "stream-scrub" (k_stream_encode's compare ending,
- * (10,4,13): one launch per stripe in every entry point), or "none". */
+ * "bs-scrub-batch" (a batch in one launch), "stream-scrub" (k_stream_encode's compare ending,
+ * (10,4,13): one launch per stripe in every entry point) and "stream-scrub-batch" (the same
+ * kernel's batch variant: many stripes in one launch, clay_set_scrub_path), or "none". */
 const char *clay_last_exec_path(void);
 
 /* Name of the path the last encode on this thread used ("fused-q4w128p8", "staged", ...). */

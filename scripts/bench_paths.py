@@ -8,6 +8,8 @@ scrub   read n*chunk (ONLY=scrub; scrub10: the (10,4,13) 1 GiB leg alone; scrub_
         auto's gate for the streaming scrub)
 ONLY=batch_stream: many (10,4,13) stripes above 4 MiB per call, the streaming batch against a
 per-stripe loop; batch_stream_gate: the sweep behind auto's upper gate for it.
+ONLY=scrub_batch_stream: many (10,4,13) stripes scrubbed in one launch of the streaming batch, the
+path without it and the batched encode alternated; scrub_batch_gate: the sweep behind auto's gate.
 Prints one JSON object per configuration."""
 import json
 import os
@@ -474,6 +476,91 @@ def batch_stream_cfg(sc, n, k=10, m=4, d=13, gate=False):
     print(json.dumps(out), flush=True)
 
 
+def _scrub_partner(sc):
+    """The exec mode under which scrub path 'auto' runs what a library without the streaming batch
+    runs for a batch of (10,4,13) at sub-chunk sc under exec auto: from 65,536 the per-stripe
+    "stream-scrub" loop ("stream"), below it one launch of v1, "bs-scrub-batch" ("grouped")."""
+    return "stream" if sc >= 65536 else "grouped"
+
+
+def scrub_batch_stream_cfg(sc, counts, with_encode=False, samples=None):
+    """ONLY=scrub_batch_stream / scrub_batch_gate: n stripes of (10,4,13) at sub-chunk sc with
+    codewords in the buffers through clay_scrub_device_strided, as ONE launch of the streaming batch
+    (scrub path 'stream-batch', "stream-scrub-batch") and as its partner (_scrub_partner), with
+    with_encode also the batched encode of the same shape into a second parity buffer; the legs'
+    samples alternate in one run.  Per leg: the samples, median, min and spread (max - min) per
+    call of n stripes.  A win: the batch's median is below the partner's by more than the spread
+    of the partner's samples."""
+    global RUNS
+    c = ClayCode(10, 4, 13)
+    k, m = 10, 4
+    chunk = c.sub_chunk_no * sc
+    nmax = max(counts)
+    data = rnd(nmax * k, chunk, 23).view(nmax, k, chunk)
+    par = torch.empty((nmax, m, chunk), dtype=torch.uint8, device="cuda")
+    c.encode_device_strided(data, par, nmax, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+    par2 = torch.empty((nmax, m, chunk), dtype=torch.uint8, device="cuda") if with_encode else None
+    res = torch.empty(nmax, dtype=torch.int32, device="cuda")
+    partner = _scrub_partner(sc)
+    keep = RUNS
+    if samples:
+        RUNS = samples
+    try:
+        for n in counts:
+            def scrub(mode, path):
+                def fn():
+                    clay_amd.set_exec_mode(mode)
+                    clay_amd.set_scrub_path(path)
+                    c.scrub_device_strided(data, par, res, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+                return fn
+
+            def encode():
+                c.encode_device_strided(data, par2, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+
+            legs = [("batch", scrub("auto", "stream-batch")), ("partner", scrub(partner, "auto"))]
+            if with_encode:
+                legs.append(("encode", encode))
+            info = {}
+            for tag, fn in legs:
+                res.fill_(-1)
+                fn()
+                torch.cuda.synchronize()
+                if tag == "encode":
+                    info[tag] = (clay_amd.last_encode_path(), clay_amd.last_launch_count())
+                    assert torch.equal(par2[:n], par[:n])
+                else:
+                    info[tag] = (clay_amd.last_exec_path(), clay_amd.last_launch_count())
+                    assert not bool(res[:n].any().item()) and bool((res[n:] == -1).all().item())
+            ts = {tag: [] for tag, _ in legs}
+            for i in range(RUNS + 2):
+                for tag, fn in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    fn()
+                    e0.record(stream)
+                    for _ in range(B2B):
+                        fn()
+                    e1.record(stream)
+                    torch.cuda.synchronize()
+                    if i >= 2:
+                        ts[tag].append(e0.elapsed_time(e1) / B2B)
+            out = {"config": f"scrub (10,4,13) batch_stream {n} x {k * chunk / 2**20:.1f} MiB (sc {sc})",
+                   "stripe_data_bytes": n * k * chunk, "partner_exec_mode": partner}
+            for tag, _ in legs:
+                t = ts[tag]
+                med = float(np.median(t))
+                out[tag] = {"path": info[tag][0], "launches": info[tag][1],
+                            "us": [round(x * 1e3, 2) for x in t], "median_us": round(med * 1e3, 2),
+                            "min_us": round(float(np.min(t)) * 1e3, 2),
+                            "spread_us": round(float(np.max(t) - np.min(t)) * 1e3, 2),
+                            "stripe_data_GiBps": round(n * k * chunk / (med * 1e-3) / 2**30, 1)}
+            out["batch_wins"] = bool(out["partner"]["median_us"] - out["batch"]["median_us"] > out["partner"]["spread_us"])
+            print(json.dumps(out), flush=True)
+    finally:
+        RUNS = keep
+        clay_amd.set_exec_mode(EXEC)
+        clay_amd.set_scrub_path("auto")
+
+
 def repair_cfg(k, m, d, chunk, lost):
     c = ClayCode(k, m, d)
     sc = chunk // c.sub_chunk_no
@@ -539,6 +626,21 @@ if __name__ == "__main__":
             ("scrub10", lambda: scrub_cfg(10, 4, 13, 1 << 30, ["auto", "stream", "grouped"])),
             # ONLY=scrub_gate: the sweep behind auto's gate for the streaming scrub
             ("scrub_gate", scrub_gate_cfg),
+            # ONLY=scrub_batch_stream: many (10,4,13) stripes scrubbed in one launch of the streaming
+            # batch, against the path without it and the batched encode of the same shape
+            *[("scrub_batch_stream", (lambda sc=sc, n=n: scrub_batch_stream_cfg(sc, [n], with_encode=True)))
+              for sc, n in ((6560, 64), (2048, 205), (26216, 16))],
+            # ONLY=scrub_batch_gate: the sweep behind auto's gate for it: at least 5
+            # samples per leg; the last count of the small sizes is about 1 GiB of data
+            *[("scrub_batch_gate", (lambda sc=sc: scrub_batch_stream_cfg(
+                sc, [2, 4, 8, 32, 64, round(2**30 / (2560 * sc))], samples=max(5, RUNS // 2))))
+              for sc in (2048, 4096, 8192, 16384, 32768)],
+            *[("scrub_batch_gate", (lambda sc=sc: scrub_batch_stream_cfg(sc, [2, 3, 4, 6], samples=max(5, RUNS // 2))))
+              for sc in (65536, 66176, 131080, 262152, 419432)],
+            # ONLY=scrub_batch_fill: between the sweep's 16 and 32 workgroups per XCD (of 32): 20, 24,
+            # 28 at sc 2,048, 20, 25, 30 at sc 8,216 (5 per stripe), 26 at sc 26,216 (13 per stripe)
+            *[("scrub_batch_fill", (lambda sc=sc, ns=ns: scrub_batch_stream_cfg(sc, ns, samples=max(5, RUNS // 2))))
+              for sc, ns in ((2048, [20, 24, 28]), (8216, [4, 5, 6]), (26216, [2, 3, 4]))],
             ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 1 << 10, 65536, 1024)),
             ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 10 << 10, 6553, 1024)),
             ("scrub", lambda: scrub_batch_cfg(4, 2, 5, 100 << 10, 655, 655)),
