@@ -225,7 +225,8 @@ struct BsArgs {
     uint64_t sc;                     // sub-chunk bytes (v1: any; bs6 / stream: multiple of 8)
     uint32_t ntiles, tiles_per_xcd, nslots;
     // k_bs_encode batches: stripe s's nodes at data[i] + s * sdata, par[x] + s * spar
-    // (ntiles tiles per stripe, tiles_per_xcd over all nstripes * ntiles); 0 = one stripe.
+    // (ntiles tiles per stripe, tiles_per_xcd over all nstripes * ntiles); the host passes 1 for
+    // one stripe (0 is read as 1).
     // k_stream_encode BATCH (stream_batch_kernels.hip): the same nstripes / sdata / spar;
     // tiles_per_xcd = one stripe's XCD region, nslots = one stripe's workgroups per XCD and
     // ntiles = the groups of nslots workgroups per XCD (grid = 8 * ntiles * nslots; the other

@@ -4,9 +4,7 @@
 // The host-side planning (erasure pattern -> DecArgs) is in engine.hip.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <set>
-
+#include "lds_attr.hpp"
 #include "stream_local256.hpp"
 
 #ifndef LOCAL256_ANY
@@ -20,17 +18,8 @@ constexpr bool kAny = LOCAL256_ANY != 0;
 template <int KD, int G, int NE>
 static hipError_t launch_l256(const bs::DecArgs &a, hipStream_t stream, int dev) {
     using Kn = bs::Local256<KD, G, NE, kAny>;
-    static std::mutex mu;
-    static std::set<int> done;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bs::k_stream_local256<KD, G, NE, kAny>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(&bs::k_stream_local256<KD, G, NE, kAny>), Kn::LDS_BYTES, dev))
+        return e;
     bs::k_stream_local256<KD, G, NE, kAny><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();
 }

@@ -5,10 +5,7 @@
 
 #include <cstdlib>
 
-#include <mutex>
-#include <set>
-#include <utility>
-
+#include "lds_attr.hpp"
 #include "stream_decode.hpp"
 #include "stream_local.hpp"
 #include "stream_fused2.hpp"
@@ -19,17 +16,8 @@ namespace clay {
 template <int KD, int G>
 static hipError_t launch_local(const bs::DecArgs &a, hipStream_t stream, int dev) {
     using Kn = bs::StreamDec<KD, G>;
-    static std::mutex mu;
-    static std::set<int> done;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bs::k_stream_local<KD, G>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(&bs::k_stream_local<KD, G>), Kn::LDS_BYTES, dev))
+        return e;
     bs::k_stream_local<KD, G><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();
 }
@@ -58,18 +46,9 @@ hipError_t launch_stream_local_kernel(int kd, int g, const bs::DecArgs &a, hipSt
 
 template <int KD, int PROBE = 0, bool TWO = false>
 static hipError_t launch_f2(const bs::DecArgs &a, hipStream_t stream, int dev) {
-    static std::mutex mu;
-    static std::set<int> done;
     const int lds = int(a.ring + a.ne) * bs::kDecBuf;  // ring + S/C region (ne rows)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bs::k_stream_fused2<KD, 3, PROBE, TWO>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(&bs::k_stream_fused2<KD, 3, PROBE, TWO>), 160 * 1024, dev))
+        return e;
     bs::k_stream_fused2<KD, 3, PROBE, TWO><<<dim3(a.nslots * 8), dim3(bs::StreamDec<KD, 3>::BLOCK), lds, stream>>>(a);
     return hipGetLastError();
 }

@@ -2,9 +2,7 @@
 // (stream_encode3.hpp), in their own translation unit so they compile in parallel.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <set>
-
+#include "lds_attr.hpp"
 #include "stream_encode3.hpp"
 
 namespace clay {
@@ -12,17 +10,8 @@ namespace clay {
 template <int L>
 static hipError_t launch3(const bs::Enc3Args &a, hipStream_t stream, int dev) {
     using Kn = bs::StreamEnc3<9, 3, L>;
-    static std::mutex mu;
-    static std::set<int> done;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bs::k_stream_encode3<9, 3, L>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(&bs::k_stream_encode3<9, 3, L>), Kn::LDS_BYTES, dev))
+        return e;
     bs::k_stream_encode3<9, 3, L><<<dim3(a.ns * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();
 }

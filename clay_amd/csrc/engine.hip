@@ -39,6 +39,7 @@
 #include "line_args.hpp"  // line-local bit-sliced (4,2,5) encode / single-erasure decode: bitslice_line.hpp, in line_kernels.hip
 #include "scrub_args.hpp"  // compare-ending instantiations of the two bit-sliced encodes, in scrub_kernels.hip
 #include "kernels.hpp"
+#include "lds_attr.hpp"
 #include "plan.hpp"
 #include "tuning.hpp"
 #include "encode3_args.hpp"
@@ -556,6 +557,8 @@ struct DevProps {
     int dev = 0;
     int cus = 256;
     hipDeviceProp_t raw{};
+    // workgroups per XCD at one per CU (8 XCDs)
+    uint32_t per_xcd() const { return uint32_t(std::max(1, cus / 8)); }
 };
 static DevProps g_props[64];
 static std::once_flag g_props_once[64];
@@ -568,15 +571,12 @@ static const DevProps &dev_props(int dev) {
     return g_props[dev];
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device)
-static Error lds_attr_once(const void *fn, int bytes, int dev) {
-    static std::mutex mu;
-    static std::set<std::pair<const void *, int>> done;
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.count({fn, dev})) return Error{};
-    CLAY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done.insert({fn, dev});
-    return Error{};
+// lds_attr_once (lds_attr.hpp) as an Error, worded as CLAY_HIP words the HIP call it makes
+static Error lds_attr(const void *fn, int bytes, int dev) {
+    const hipError_t e = lds_attr_once(fn, bytes, dev);
+    if (e == hipSuccess) return Error{};
+    return make_error(CLAY_ERR_DEVICE, size_t(e), 0, 0, "HIP error: %s (%s)", hipGetErrorString(e),
+                      "hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)");
 }
 
 static bool capturing(hipStream_t st) {
@@ -1148,7 +1148,88 @@ static bool misaligned8(T *const *p, size_t n, int64_t stride = 0) {
 template <class Args>
 static void line_slots(Args &a, uint64_t tiles, const DevProps &prop) {
     a.tiles_per_xcd = uint32_t((tiles + 7) / 8);
-    a.nslots = std::min(a.tiles_per_xcd, uint32_t(std::max(1, prop.cus / 8) * 8));
+    a.nslots = std::min(a.tiles_per_xcd, prop.per_xcd() * 8);
+}
+
+// The kernel arguments of the three bit-sliced encode families, each filled in one place for the
+// encode and the compare-ending (scrub) launchers, one stripe and batches alike: ns stripes at
+// stripe 0's pointers + s * sdata / spar (one stripe: ns = 1 and strides of 0), res the scrub's
+// result word of stripe 0 (nullptr for an encode).  The fills store ns in nstripes, so one stripe
+// travels as 1 (the kernels read 0 as 1, and the clear-mode launches leave it 0).
+
+// v1, k_bs_encode<KD, M, PG>: nullptr for the shortened nodes, the tiles of all stripes flattened
+// and cut into 8 XCD runs, as many workgroups per CU as the kernel's LDS allows.  *bt: byte tails.
+// false: more (stripe, tile) pairs than the kernel's 32-bit flattening holds.
+template <int KD, int M, int PG>
+static bool bs_args(const DevProps &prop, const uint8_t *const *data0, uint8_t *const *par0, int64_t sdata, int64_t spar,
+                    size_t ns, size_t sc, uint32_t *res, bs::BsArgs &a, bool *bt) {
+    using Kn = bs::BsKernel<KD, M, PG>;
+    const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
+    if (ntiles * ns >= 0xFFFFFFFFull) return false;
+    const int per_cu = std::max(1, int((160 * 1024) / (Kn::LDS_WORDS * 4)));
+    a = bs::BsArgs{};
+    for (int i = 0; i < Kn::S::K; i++) a.data[i] = i < KD ? data0[i] : nullptr;
+    for (int x = 0; x < M; x++) a.par[x] = par0[x];
+    a.sc = sc;
+    a.ntiles = uint32_t(ntiles);
+    a.nstripes = uint32_t(ns);
+    a.sdata = sdata;
+    a.spar = spar;
+    a.res = res;
+    a.tiles_per_xcd = uint32_t((ntiles * ns + 7) / 8);
+    a.nslots = std::min(prop.per_xcd() * uint32_t(per_cu), a.tiles_per_xcd);
+    *bt = sc % 8 != 0 || misaligned8(a.data, KD, sdata) || misaligned8(a.par, M, spar);
+    return true;
+}
+
+// The line kernel, k_bs_encode1 for a (k, m) code on tiles of W positions (bitslice_line.hpp).
+// *bt and false: as bs_args.
+static bool line_args(const DevProps &prop, size_t k, size_t m, size_t W, const uint8_t *const *data0,
+                      uint8_t *const *par0, int64_t sdata, int64_t spar, size_t ns, size_t sc, uint32_t *res,
+                      bs::Enc1Args &a, bool *bt) {
+    const uint64_t ntiles = (sc + W - 1) / W;
+    if (ntiles * ns >= 0xFFFFFFFFull) return false;
+    a = bs::Enc1Args{};
+    for (size_t i = 0; i < k; i++) a.data[i] = data0[i];
+    for (size_t x = 0; x < m; x++) a.par[x] = par0[x];
+    a.sc = sc;
+    a.ntiles = uint32_t(ntiles);
+    a.nstripes = uint32_t(ns);
+    a.sdata = sdata;
+    a.spar = spar;
+    a.res = res;
+    line_slots(a, ntiles * ns, prop);
+    *bt = sc % 8 != 0 || misaligned8(a.data, k, sdata) || misaligned8(a.par, m, spar);
+    return true;
+}
+
+// Sub-chunk sizes k_stream_encode takes for (10,4,13) and (9,4,12): 8-byte rows, a clamped 16-byte
+// piece, and 32-bit chunk offsets in the lanes (256 layers of sc bytes)
+static bool stream_sc_ok(size_t sc) { return sc % 8 == 0 && sc >= 16 && double(256) * double(sc) < 4294967296.0; }
+
+// k_stream_encode<KD, ..> (stream_encode.hpp): the XCD cut of one stripe (stream_cut: the region in
+// tiles_per_xcd, one workgroup per 256-byte tile of it and at most one per CU).  groups = 0: the
+// one-stripe instantiations, which ignore ntiles, nstripes and the strides; else the BATCH ones
+// with that many groups of nslots workgroups per XCD (stream_batch_geometry).  The caller has
+// checked the shape (stream_sc_ok, 8-byte aligned rows).
+template <int KD>
+static bs::BsArgs stream_args(const DevProps &prop, const uint8_t *const *data0, uint8_t *const *par0, int64_t sdata,
+                              int64_t spar, size_t ns, uint32_t groups, size_t sc, uint32_t *res) {
+    using S = typename bs::StreamEnc<KD, 4>::S;
+    static_assert(S::ALPHA == 256, "stream_sc_ok bounds the chunk offsets of 256 layers");
+    const bs::StreamCut cut = bs::stream_cut(sc, prop.per_xcd());
+    bs::BsArgs a{};
+    for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? data0[i] : nullptr;
+    for (int x = 0; x < 4; x++) a.par[x] = par0[x];
+    a.sc = sc;
+    a.tiles_per_xcd = cut.region;
+    a.nslots = cut.nslots;
+    a.ntiles = groups;
+    a.nstripes = uint32_t(ns);
+    a.sdata = sdata;
+    a.spar = spar;
+    a.res = res;
+    return a;
 }
 
 template <int VW, int MAXD>
@@ -1216,7 +1297,7 @@ template <int VW, int MAXD, int NWV>
 static Error launch_texec2(const ExecPtrs &ptrs, const CodeState::DevGrouped &g, const uint32_t *tabs,
                            uint32_t nstages, uint64_t sc, uint32_t ubase, hipStream_t stream, int dev) {
     const size_t lds = size_t(g.nu) * 64 * VW + kTexTabBytes;
-    Error e = lds_attr_once(reinterpret_cast<const void *>(&k_texec<VW, MAXD, NWV>), int(kTexLdsMax), dev);
+    Error e = lds_attr(reinterpret_cast<const void *>(&k_texec<VW, MAXD, NWV>), int(kTexLdsMax), dev);
     if (e) return e;
     const uint64_t tiles = (sc + 64 * VW - 1) / (64 * VW);
     k_texec<VW, MAXD, NWV><<<dim3(uint32_t(tiles)), dim3(64 * NWV), lds, stream>>>(ptrs, g.terms, g.wbeg, tabs,
@@ -1329,7 +1410,7 @@ template <int Q, int PPT>
 static Error launch_fused(const FusedArgs &a, const uint32_t *mtab, size_t lds, hipStream_t stream, int grid) {
     int dev = 0;
     CLAY_HIP(hipGetDevice(&dev));
-    Error e = lds_attr_once(reinterpret_cast<const void *>(&k_fused_encode<Q, PPT>), int(kFusedLdsBudget), dev);
+    Error e = lds_attr(reinterpret_cast<const void *>(&k_fused_encode<Q, PPT>), int(kFusedLdsBudget), dev);
     if (e) return e;
     k_fused_encode<Q, PPT><<<dim3(grid), dim3(kFusedBlock), lds, stream>>>(a, mtab);
     CLAY_HIP(hipGetLastError());
@@ -1416,24 +1497,18 @@ static Error encode_fused(CodeState &cs, DevState &ds, int dev, const uint8_t *c
 // Bit-sliced fused encode (bitslice.hpp): compile-time instantiations per code.
 // ---------------------------------------------------------------------------
 template <int KD, int M, int PG>
-static Error launch_bs(CodeState &cs, const hipDeviceProp_t &prop, const uint8_t *const *data, uint8_t *const *par,
+static Error launch_bs(CodeState &cs, const DevProps &prop, const uint8_t *const *data, uint8_t *const *par,
                        size_t n_stripes, size_t sc, hipStream_t stream, bool *done) {
     using Kn = bs::BsKernel<KD, M, PG>;
     using S = typename Kn::S;
     const clay_code_t &c = cs.code;
     if (int(c.k) != KD || int(c.m) != M || int(c.d) != KD + M - 1) return Error{};
     if (Error e = rs_matches<S, M>(cs)) return e;
-    const int per_cu = std::max(1, int((160 * 1024) / (Kn::LDS_WORDS * 4)));
     for (size_t s = 0; s < n_stripes; s++) {
-        bs::BsArgs a{};
-        for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? data[s * KD + i] : nullptr;
-        for (int x = 0; x < M; x++) a.par[x] = par[s * M + x];
-        a.sc = sc;
-        a.ntiles = uint32_t((sc + Kn::W - 1) / Kn::W);
-        a.tiles_per_xcd = (a.ntiles + 7) / 8;
-        const uint32_t max_slots = uint32_t(std::max(1, prop.multiProcessorCount / 8) * per_cu);
-        a.nslots = std::min(max_slots, a.tiles_per_xcd);
-        const bool bt = sc % 8 != 0 || misaligned8(a.data, KD) || misaligned8(a.par, M);  // byte tails
+        bs::BsArgs a;
+        bool bt = false;
+        // (a sub-chunk of more tiles than 32 bits count is left to the other encode paths)
+        if (!bs_args<KD, M, PG>(prop, data + s * KD, par + s * M, 0, 0, 1, sc, nullptr, a, &bt)) return Error{};
         if (bt) bs::k_bs_encode<KD, M, PG, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
         else bs::k_bs_encode<KD, M, PG><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
         CLAY_HIP(hipGetLastError());
@@ -1454,25 +1529,15 @@ static Error launch_stream(CodeState &cs, const DevProps &prop, const uint8_t *c
     using S = typename Kn::S;
     const clay_code_t &c = cs.code;
     if (int(c.k) != KD || c.m != 4 || c.d != c.k + 3) return Error{};
-    // per-lane DMA offsets are 32-bit chunk offsets; a clamped 16-byte piece needs sc >= 16
-    if (double(S::ALPHA) * double(sc) >= 4294967296.0 || sc < 16) return Error{};
+    // (the caller has checked the rows' alignment)
+    if (!stream_sc_ok(sc)) return Error{};
     if (Error e = rs_matches<S, 4>(cs)) return e;
-    Error ae = lds_attr_once(reinterpret_cast<const void *>(&bs::k_stream_encode<KD, LOADERS, 0, bs::kStreamEncMap>),
-                             Kn::LDS_BYTES, prop.dev);
+    Error ae = lds_attr(reinterpret_cast<const void *>(&bs::k_stream_encode<KD, LOADERS, 0, bs::kStreamEncMap>),
+                        Kn::LDS_BYTES, prop.dev);
     if (ae) return ae;
-    // XCD region: sc / 8 rounded up to 32 bytes; one workgroup per CU
-    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
-    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
-    const uint32_t nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
     for (size_t s = 0; s < n_stripes; s++) {
-        bs::BsArgs a{};
-        for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? data[s * KD + i] : nullptr;
-        for (int x = 0; x < 4; x++) a.par[x] = par[s * 4 + x];
-        a.sc = sc;
-        a.tiles_per_xcd = region;
-        a.nslots = nslots;
-        a.ntiles = 0;
-        bs::k_stream_encode<KD, LOADERS, 0, bs::kStreamEncMap><<<dim3(nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
+        const bs::BsArgs a = stream_args<KD>(prop, data + s * KD, par + s * 4, 0, 0, 1, 0, sc, nullptr);
+        bs::k_stream_encode<KD, LOADERS, 0, bs::kStreamEncMap><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
         CLAY_HIP(hipGetLastError());
         t_last_launches++;
     }
@@ -1493,11 +1558,11 @@ static Error launch_stream3(CodeState &cs, const DevProps &prop, const uint8_t *
     const clay_code_t &c = cs.code;
     if (c.k != 9 || c.m != 3 || c.d != 11 || sc < 16 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
     if (Error e = rs_matches<S, 3>(cs)) return e;
-    const uint32_t W = 512;
+    const bs::StreamCut cut = bs::stream_cut(sc, prop.per_xcd(), 512);
     bs::Enc3Args a{};
     a.sc = sc;
-    a.region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
-    a.ns = std::min(uint32_t(std::max(1, prop.cus / 8)), std::max(1u, (a.region + W - 1) / W));
+    a.region = cut.region;
+    a.ns = cut.nslots;
     for (size_t s = 0; s < n_stripes; s++) {
         for (int i = 0; i < 9; i++) a.data[i] = data[s * 9 + i];
         for (int x = 0; x < 3; x++) a.par[x] = par[s * 3 + x];
@@ -1520,13 +1585,10 @@ static Error launch_bs_encode1(CodeState &cs, const DevProps &prop, const uint8_
     if (!W || c.d != c.k + c.m - 1 || c.nu != 0 || sc == 0) return Error{};
     if (Error e = rs_matches<bs::Shape<4, 2>, 2>(cs)) return e;
     for (size_t s = 0; s < n_stripes; s++) {
-        bs::Enc1Args a{};
-        for (size_t i = 0; i < c.k; i++) a.data[i] = data[s * c.k + i];
-        for (size_t x = 0; x < c.m; x++) a.par[x] = par[s * c.m + x];
-        const bool bt = sc % 8 != 0 || misaligned8(a.data, c.k) || misaligned8(a.par, c.m);
-        a.sc = sc;
-        a.ntiles = uint32_t((sc + size_t(W) - 1) / size_t(W));
-        line_slots(a, a.ntiles, prop);
+        bs::Enc1Args a;
+        bool bt = false;
+        // (a sub-chunk of more tiles than 32 bits count is left to the other encode paths)
+        if (!line_args(prop, c.k, c.m, size_t(W), data + s * c.k, par + s * c.m, 0, 0, 1, sc, nullptr, a, &bt)) return Error{};
         CLAY_HIP(launch_bs_encode1_kernel(int(c.k), int(c.m), bt, a, stream));
         t_last_launches++;
     }
@@ -1576,14 +1638,14 @@ static Error encode_bitsliced(CodeState &cs, int dev, const uint8_t *const *data
     // v1 (register loads, PG x 32 positions per lane): every q = m code it is instantiated for
     switch (key) {
     case 1004:
-        if (tile == 1) e = launch_bs<10, 4, 1>(cs, prop.raw, data, par, n_stripes, sc, stream, done);
-        else if (tile == 4) e = launch_bs<10, 4, 4>(cs, prop.raw, data, par, n_stripes, sc, stream, done);
-        else e = launch_bs<10, 4, 2>(cs, prop.raw, data, par, n_stripes, sc, stream, done);
+        if (tile == 1) e = launch_bs<10, 4, 1>(cs, prop, data, par, n_stripes, sc, stream, done);
+        else if (tile == 4) e = launch_bs<10, 4, 4>(cs, prop, data, par, n_stripes, sc, stream, done);
+        else e = launch_bs<10, 4, 2>(cs, prop, data, par, n_stripes, sc, stream, done);
         break;
-    case 402: e = launch_bs<4, 2, 64>(cs, prop.raw, data, par, n_stripes, sc, stream, done); break;
-    case 804: e = launch_bs<8, 4, 8>(cs, prop.raw, data, par, n_stripes, sc, stream, done); break;
-    case 903: e = launch_bs<9, 3, 6>(cs, prop.raw, data, par, n_stripes, sc, stream, done); break;
-    case 603: e = launch_bs<6, 3, 16>(cs, prop.raw, data, par, n_stripes, sc, stream, done); break;
+    case 402: e = launch_bs<4, 2, 64>(cs, prop, data, par, n_stripes, sc, stream, done); break;
+    case 804: e = launch_bs<8, 4, 8>(cs, prop, data, par, n_stripes, sc, stream, done); break;
+    case 903: e = launch_bs<9, 3, 6>(cs, prop, data, par, n_stripes, sc, stream, done); break;
+    case 603: e = launch_bs<6, 3, 16>(cs, prop, data, par, n_stripes, sc, stream, done); break;
     default: break;
     }
     return e;
@@ -1728,22 +1790,15 @@ static Error launch_bs_batch(CodeState &cs, int dev, const uint8_t *const *data0
     using Kn = bs::BsKernel<KD, M, PG>;
     using S = typename Kn::S;
     if (Error e = rs_matches<S, M>(cs)) return e;
-    const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
     // sub-chunks well under a tile would leave most lanes idle: the staged batch packs them
-    if (sc < uint64_t(Kn::W) / 2 || ntiles * ns >= 0xFFFFFFFFull) return Error{};
+    if (sc < uint64_t(Kn::W) / 2) return Error{};
+    const DevProps &prop = dev_props(dev);
+    bool bt = false;  // byte tails
     if constexpr (KD == 4 && M == 2) {
         // (4,2,5): the line-local kernel (bitslice_line.hpp), same 2048-position tiles
-        bs::Enc1Args e{};
-        for (int i = 0; i < KD; i++) e.data[i] = data0[i];
-        for (int x = 0; x < M; x++) e.par[x] = par0[x];
-        e.sc = sc;
-        e.ntiles = uint32_t(ntiles);
-        e.nstripes = uint32_t(ns);
-        e.sdata = sdata;
-        e.spar = spar;
-        line_slots(e, ntiles * ns, dev_props(dev));
-        const bool bt1 = sc % 8 != 0 || misaligned8(e.data, KD, sdata) || misaligned8(e.par, M, spar);
-        CLAY_HIP(launch_bs_encode1_kernel(KD, M, bt1, e, stream));
+        bs::Enc1Args e;
+        if (!line_args(prop, KD, M, Kn::W, data0, par0, sdata, spar, ns, sc, nullptr, e, &bt)) return Error{};
+        CLAY_HIP(launch_bs_encode1_kernel(KD, M, bt, e, stream));
         t_last_launches++;
         char buf1[64];
         std::snprintf(buf1, sizeof(buf1), "bitsliced-batch-line-k%dm%d-w%d", KD, M, Kn::W);
@@ -1751,19 +1806,8 @@ static Error launch_bs_batch(CodeState &cs, int dev, const uint8_t *const *data0
         *done = true;
         return Error{};
     }
-    const int per_cu = std::max(1, int((160 * 1024) / (Kn::LDS_WORDS * 4)));
-    bs::BsArgs a{};
-    for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? data0[i] : nullptr;
-    for (int x = 0; x < M; x++) a.par[x] = par0[x];
-    a.sc = sc;
-    a.ntiles = uint32_t(ntiles);
-    a.nstripes = uint32_t(ns);
-    a.sdata = sdata;
-    a.spar = spar;
-    a.tiles_per_xcd = uint32_t((ntiles * ns + 7) / 8);
-    const uint32_t max_slots = uint32_t(std::max(1, dev_props(dev).raw.multiProcessorCount / 8) * per_cu);
-    a.nslots = std::min(max_slots, a.tiles_per_xcd);
-    const bool bt = sc % 8 != 0 || misaligned8(a.data, KD, sdata) || misaligned8(a.par, M, spar);  // byte tails
+    bs::BsArgs a;
+    if (!bs_args<KD, M, PG>(prop, data0, par0, sdata, spar, ns, sc, nullptr, a, &bt)) return Error{};
     if (bt) bs::k_bs_encode<KD, M, PG, true><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
     else bs::k_bs_encode<KD, M, PG><<<dim3(a.nslots * 8), dim3(Kn::BLOCK), 0, stream>>>(a);
     CLAY_HIP(hipGetLastError());
@@ -1799,32 +1843,23 @@ static Error encode_bs_batch(CodeState &cs, int dev, const StripeOperands &data,
 hipError_t launch_stream_batch_kernel(int kd, const bs::BsArgs &a, hipStream_t stream, int dev);  // stream_batch_kernels.hip
 
 // Batched streaming encode (k_stream_encode BATCH, stream_batch_kernels.hip) for (10,4,13) and
-// (9,4,12): ONE launch for ns >= 2 stripes at uniform strides.  Every stripe keeps launch_stream's
-// cut (region, nsS workgroups per XCD); the per_xcd workgroups of an XCD form G groups of nsS, and
-// group j runs stripes j, j + G, ... back to back (BatchMap, stream_tile_map.hpp).  No allocation,
-// no pointer table: stripe 0's pointers and the two strides travel in the kernel arguments.
-// Anything it does not take (a chunk off the stride, rows off 8-byte alignment, odd sc) leaves
-// *done false and the caller goes on as before.
+// (9,4,12): ONE launch for ns >= 2 stripes at uniform strides.  Every stripe keeps the one-stripe
+// cut (stream_cut: region, nsS workgroups per XCD); the per_xcd workgroups of an XCD form G groups
+// of nsS, and group j runs stripes j, j + G, ... back to back (BatchMap, stream_tile_map.hpp).  No
+// allocation, no pointer table: stripe 0's pointers and the two strides travel in the kernel
+// arguments.  Anything it does not take (a chunk off the stride, rows off 8-byte alignment, odd sc)
+// leaves *done false and the caller goes on as before.
 // The launch geometry of k_stream_encode BATCH, for the batched encode and the batched scrub:
-// one stripe's cut as launch_stream (region, nslots workgroups per XCD) and G groups of nslots
-// workgroups per XCD, into a.sc / tiles_per_xcd / nslots / ntiles / nstripes.  false: the kernel
-// cannot take the batch (fewer than 2 stripes, more than its 32-bit stripe index holds, or more
-// steps for one workgroup than its int step counter)
-static bool stream_batch_geometry(const DevProps &prop, size_t ns, size_t sc, bs::BsArgs &a) {
+// *groups = the G groups of nslots workgroups per XCD that run one stripe's cut (stream_cut) side
+// by side, for stream_args.  false: the kernel cannot take the batch (fewer than 2 stripes, more
+// than its 32-bit stripe index holds, or more steps for one workgroup than its int step counter)
+static bool stream_batch_geometry(const DevProps &prop, size_t ns, size_t sc, uint32_t *groups) {
     if (ns < 2 || ns > 0xFFFFFFFFull) return false;
-    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
-    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
-    const uint32_t nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
-    const uint32_t groups = bs::batch_groups(per_xcd, nslots, uint32_t(ns));
+    const bs::StreamCut cut = bs::stream_cut(sc, prop.per_xcd());
+    *groups = bs::batch_groups(prop.per_xcd(), cut.nslots, uint32_t(ns));
     // a workgroup's steps (12 per tile) are counted in an int: rounds per stripe x stripes per group
-    const uint64_t rounds = (uint64_t(region) + uint64_t(nslots) * 256u - 1u) / (uint64_t(nslots) * 256u);
-    if (rounds * ((ns + groups - 1) / groups) * 12u > 0x7FFFFFFFull) return false;
-    a.sc = sc;
-    a.tiles_per_xcd = region;
-    a.nslots = nslots;
-    a.ntiles = groups;
-    a.nstripes = uint32_t(ns);
-    return true;
+    const uint64_t rounds = (uint64_t(cut.region) + uint64_t(cut.nslots) * 256u - 1u) / (uint64_t(cut.nslots) * 256u);
+    return rounds * ((ns + *groups - 1) / *groups) * 12u <= 0x7FFFFFFFull;
 }
 
 template <int KD>
@@ -1833,8 +1868,7 @@ static Error launch_stream_batch(CodeState &cs, const DevProps &prop, const Stri
     using Kn = bs::StreamEnc<KD, 4>;
     using S = typename Kn::S;
     static_assert(Kn::STEPS == 12, "stream_batch_geometry counts 12 steps per tile");
-    // 8-byte rows, a clamped 16-byte piece, 32-bit chunk offsets in the lanes
-    if (sc % 8 != 0 || sc < 16 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
+    if (!stream_sc_ok(sc)) return Error{};
     if (ns < 2 || ns > 0xFFFFFFFFull) return Error{};
     // stripe-0 pointers and one stride for all data nodes, one for all parity nodes
     int64_t sdata = 0, spar = 0;
@@ -1845,12 +1879,9 @@ static Error launch_stream_batch(CodeState &cs, const DevProps &prop, const Stri
     par.stripe_ptrs(0, p0);
     if (misaligned8(d0, size_t(KD), sdata) || misaligned8(p0, 4, spar)) return Error{};
     if (Error e = rs_matches<S, 4>(cs)) return e;
-    bs::BsArgs a{};
-    if (!stream_batch_geometry(prop, ns, sc, a)) return Error{};
-    for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? d0[i] : nullptr;
-    for (int x = 0; x < 4; x++) a.par[x] = p0[x];
-    a.sdata = sdata;
-    a.spar = spar;
+    uint32_t groups = 0;
+    if (!stream_batch_geometry(prop, ns, sc, &groups)) return Error{};
+    const bs::BsArgs a = stream_args<KD>(prop, d0, p0, sdata, spar, ns, groups, sc, nullptr);
     CLAY_HIP(launch_stream_batch_kernel(KD, a, stream, prop.dev));
     t_last_launches++;
     char buf[64];
@@ -1981,19 +2012,9 @@ static Error launch_bs_scrub1(CodeState &cs, const DevProps &prop, uint8_t *cons
     *done = false;
     using Kn = bs::BsKernel<4, 2, ScrubPg<4, 2>::value>;  // the line kernel's tile is v1's
     if (Error e = rs_matches<bs::Shape<4, 2>, 2>(cs)) return e;
-    const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
-    if (ntiles * ns >= 0xFFFFFFFFull) return Error{};
-    bs::Enc1Args a{};
-    for (int i = 0; i < 4; i++) a.data[i] = data0[i];
-    for (int x = 0; x < 2; x++) a.par[x] = par0[x];
-    a.sc = sc;
-    a.ntiles = uint32_t(ntiles);
-    a.nstripes = uint32_t(ns);
-    a.sdata = sdata;
-    a.spar = spar;
-    a.res = res;
-    line_slots(a, ntiles * ns, prop);
-    const bool bt = sc % 8 != 0 || misaligned8(a.data, 4, sdata) || misaligned8(a.par, 2, spar);
+    bs::Enc1Args a;
+    bool bt = false;
+    if (!line_args(prop, 4, 2, Kn::W, data0, par0, sdata, spar, ns, sc, res, a, &bt)) return Error{};
     CLAY_HIP(launch_bs_scrub1_kernel(4, 2, bt, a, stream));
     t_last_launches++;
     *done = true;
@@ -2008,67 +2029,29 @@ static Error launch_bs_scrub(CodeState &cs, const DevProps &prop, uint8_t *const
     using Kn = bs::BsKernel<KD, M, ScrubPg<KD, M>::value>;
     using S = typename Kn::S;
     if (Error e = rs_matches<S, M>(cs)) return e;
-    const uint64_t ntiles = (sc + Kn::W - 1) / Kn::W;
-    if (ntiles * ns >= 0xFFFFFFFFull) return Error{};
-    const int per_cu = std::max(1, int((160 * 1024) / (Kn::LDS_WORDS * 4)));
-    bs::BsArgs a{};
-    for (int i = 0; i < S::K; i++) a.data[i] = i < KD ? data0[i] : nullptr;
-    for (int x = 0; x < M; x++) a.par[x] = par0[x];
-    a.sc = sc;
-    a.ntiles = uint32_t(ntiles);
-    a.nstripes = uint32_t(ns);
-    a.sdata = sdata;
-    a.spar = spar;
-    a.res = res;
-    a.tiles_per_xcd = uint32_t((ntiles * ns + 7) / 8);
-    a.nslots = std::min(uint32_t(std::max(1, prop.raw.multiProcessorCount / 8) * per_cu), a.tiles_per_xcd);
-    const bool bt = sc % 8 != 0 || misaligned8(a.data, KD, sdata) || misaligned8(a.par, M, spar);  // byte tails
+    bs::BsArgs a;
+    bool bt = false;
+    if (!bs_args<KD, M, ScrubPg<KD, M>::value>(prop, data0, par0, sdata, spar, ns, sc, res, a, &bt)) return Error{};
     CLAY_HIP(launch_bs_scrub_kernel(KD, M, bt, a, stream));
     t_last_launches++;
     *done = true;
     return Error{};
 }
 
-// (10,4,13) on the compare-ending streaming encode (stream_encode.hpp SCRUB, scrub_kernels.hip):
-// one stripe per launch, launch_stream<10, 4>'s region / nslots arithmetic.  The caller has checked
-// the shape (stream_scrub_ok)
+// (10,4,13) on the compare-ending streaming encode (stream_encode.hpp SCRUB, scrub_kernels.hip).
+// groups = 0: one stripe, one launch.  Else ns >= 2 stripes in ONE launch of the BATCH variant: the
+// batched encode's geometry (groups from stream_batch_geometry), stripe 0's pointers and the two
+// strides in the kernel arguments, res[s] the word of stripe s.  No allocation and no pointer table,
+// so a first call inside a stream capture works.  The caller has checked the shape of every stripe
+// (stream_scrub_ok) and, for a batch, the strides (uniform_stride)
 static Error launch_stream_scrub(CodeState &cs, const DevProps &prop, uint8_t *const *data0, uint8_t *const *par0,
-                                 size_t sc, uint32_t *res, hipStream_t stream) {
-    using Kn = bs::StreamEnc<10, 4>;
-    using S = typename Kn::S;
-    if (Error e = rs_matches<S, 4>(cs)) return e;
-    // XCD region: sc / 8 rounded up to 32 bytes; one workgroup per CU
-    const uint32_t region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
-    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
-    bs::BsArgs a{};
-    for (int i = 0; i < S::K; i++) a.data[i] = i < 10 ? data0[i] : nullptr;
-    for (int x = 0; x < 4; x++) a.par[x] = par0[x];
-    a.sc = sc;
-    a.tiles_per_xcd = region;
-    a.nslots = std::min(per_xcd, std::max(1u, (region + 255u) / 256u));
-    a.ntiles = 0;
-    a.res = res;
-    CLAY_HIP(launch_stream_scrub_kernel(a, stream, prop.dev));
-    t_last_launches++;
-    return Error{};
-}
-
-// ns >= 2 stripes of (10,4,13) in ONE launch of the compare-ending k_stream_encode BATCH
-// (scrub_kernels.hip): the batched encode's geometry (`a` from stream_batch_geometry), stripe 0's
-// pointers and the two strides in the kernel arguments, res[s] the word of stripe s.  No allocation
-// and no pointer table, so a first call inside a stream capture works.  The caller has checked the
-// shape of every stripe (stream_scrub_ok) and the strides (uniform_stride)
-static Error launch_stream_scrub_batch(CodeState &cs, const DevProps &prop, bs::BsArgs a, uint8_t *const *data0,
-                                       uint8_t *const *par0, int64_t sdata, int64_t spar, uint32_t *res,
-                                       hipStream_t stream) {
+                                 int64_t sdata, int64_t spar, size_t ns, uint32_t groups, size_t sc, uint32_t *res,
+                                 hipStream_t stream) {
     using S = typename bs::StreamEnc<10, 4>::S;
     if (Error e = rs_matches<S, 4>(cs)) return e;
-    for (int i = 0; i < S::K; i++) a.data[i] = i < 10 ? data0[i] : nullptr;
-    for (int x = 0; x < 4; x++) a.par[x] = par0[x];
-    a.sdata = sdata;
-    a.spar = spar;
-    a.res = res;
-    CLAY_HIP(launch_stream_scrub_batch_kernel(a, stream, prop.dev));
+    const bs::BsArgs a = stream_args<10>(prop, data0, par0, sdata, spar, ns, groups, sc, res);
+    if (groups) CLAY_HIP(launch_stream_scrub_batch_kernel(a, stream, prop.dev));
+    else CLAY_HIP(launch_stream_scrub_kernel(a, stream, prop.dev));
     t_last_launches++;
     return Error{};
 }
@@ -2092,7 +2075,7 @@ constexpr size_t kScrubStreamMinSc = 65536;
 static bool stream_scrub_ok(const clay_code_t &c, const StripeOperands &data, const StripeOperands &par,
                             size_t n_stripes, size_t sc) {
     if (c.k != 10 || c.m != 4 || c.d != 13) return false;
-    if (sc % 8 != 0 || sc < 16 || double(256) * double(sc) >= 4294967296.0) return false;
+    if (!stream_sc_ok(sc)) return false;
     auto rows8 = [&](const StripeOperands &f) {
         if (f.strided)
             return (reinterpret_cast<uintptr_t>(f.base) & 7u) == 0 && (f.node & 7) == 0 &&
@@ -2124,11 +2107,10 @@ constexpr size_t kScrubBatchMinSc = 2048;
 constexpr size_t kScrubBatchMaxSc = 66176;
 constexpr uint64_t kScrubBatchMinFill = 20;  // 256-byte tiles per XCD over the groups' first stripes
 
-// `a`: the batch's geometry (stream_batch_geometry: a.ntiles = min(G, n) groups, a.tiles_per_xcd =
-// the XCD's region in bytes)
-static bool scrub_stream_batch_auto(size_t sc, const bs::BsArgs &a) {
+// groups: the batch's min(G, n) groups per XCD (stream_batch_geometry), each over the XCD's region
+static bool scrub_stream_batch_auto(size_t sc, uint32_t groups) {
     return sc >= kScrubBatchMinSc && sc <= kScrubBatchMaxSc &&
-           uint64_t(a.ntiles) * a.tiles_per_xcd >= kScrubBatchMinFill * 256u;
+           uint64_t(groups) * bs::xcd_region(sc) >= kScrubBatchMinFill * 256u;
 }
 
 // data / par: as encode_device_impl's, both read-only here.  result: n_stripes device words, every
@@ -2182,12 +2164,12 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
     // batch variant: wherever eligible under scrub path "stream-batch", by the measured gate under
     // scrub path auto -- except exec mode "stream", which stays the per-stripe loop, the batch's A/B
     // partner.  A call that is not eligible goes on exactly as without the batch
-    bs::BsArgs batch_args{};
+    uint32_t bgroups = 0;
     int64_t bsdata = 0, bspar = 0;
     const bool want_batch =
-        stream_shape && stream_batch_geometry(prop, n_stripes, sc, batch_args) &&  // 2 stripes or more
+        stream_shape && stream_batch_geometry(prop, n_stripes, sc, &bgroups) &&  // 2 stripes or more
         (g_scrub_path.load(std::memory_order_relaxed) == kScrubPathStreamBatch ||
-         (xm != kExecStream && scrub_stream_batch_auto(sc, batch_args)));
+         (xm != kExecStream && scrub_stream_batch_auto(sc, bgroups)));
     const bool batched = want_batch && uniform_stride(data, 0, n_stripes, nullptr, c.k, &bsdata) &&
                          uniform_stride(par, 0, n_stripes, nullptr, c.m, &bspar);
     auto launch = [&](uint8_t *const *d0, uint8_t *const *p0, int64_t sdata, int64_t spar, size_t ns, uint32_t *res,
@@ -2225,7 +2207,7 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
     if (batched) {
         data.stripe_ptrs(0, d0.data());
         par.stripe_ptrs(0, p0.data());
-        e = launch_stream_scrub_batch(cs, prop, batch_args, d0.data(), p0.data(), bsdata, bspar, result, st);
+        e = launch_stream_scrub(cs, prop, d0.data(), p0.data(), bsdata, bspar, n_stripes, bgroups, sc, result, st);
         if (e) return e;
         t_last_exec = "stream-scrub-batch";
         return Error{};
@@ -2235,7 +2217,7 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
         for (size_t s = 0; s < n_stripes; s++) {
             data.stripe_ptrs(s, d0.data());
             par.stripe_ptrs(s, p0.data());
-            e = launch_stream_scrub(cs, prop, d0.data(), p0.data(), sc, result + s, st);
+            e = launch_stream_scrub(cs, prop, d0.data(), p0.data(), 0, 0, 1, 0, sc, result + s, st);
             if (e) return e;
         }
         t_last_exec = "stream-scrub";
@@ -2453,13 +2435,13 @@ static Error launch_stream_local(CodeState &cs, const DevProps &prop, const uint
     a.g2 = g2;
     if (g2 >= 0) a.x2 = uint32_t(__builtin_ctz(a.emask[g2]));
     perm_table(gamma_det_inv(), &tabs[bs::kDecDetInv * 8]);  // (1 + gamma^2)^-1, transforms.rs:108-125
-    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
     // the 256-byte-run kernel: XCD regions of whole 32-byte units and 256-byte tiles as the encode's
     if (w256) {
-        a.region = uint32_t(((sc + 7) / 8 + 31) / 32 * 32);
-        a.nslots = std::min(per_xcd, std::max(1u, (a.region + 255u) / 256u));
+        const bs::StreamCut cut = bs::stream_cut(sc, prop.per_xcd());
+        a.region = cut.region;
+        a.nslots = cut.nslots;
     } else {
-        a.nslots = std::min(per_xcd, std::max(1u, a.region / 64u));
+        a.nslots = std::min(prop.per_xcd(), std::max(1u, a.region / 64u));
     }
     e = dec_tables(cs, prop, tabs, stream, &a.tabs);
     if (e) return e;
@@ -2599,8 +2581,7 @@ static Error launch_stream_fused2(CodeState &cs, const DevProps &prop, const uin
         if (y > 0 && (a.sec_off[y] - a.sec_off[y - 1]) + ny > RB) a.split |= 1u << y;
     }
     a.ring = RB;
-    const uint32_t per_xcd = uint32_t(std::max(1, prop.cus / 8));
-    a.nslots = std::min(per_xcd, std::max(1u, a.region / 64u));
+    a.nslots = std::min(prop.per_xcd(), std::max(1u, a.region / 64u));
     e = dec_tables(cs, prop, tabs, stream, &a.tabs);
     if (e) return e;
     if (!two) a.split = 0;  // (no pattern with one erasure per section overflows the ring)

@@ -27,7 +27,8 @@ struct Enc1Args {
     uint64_t sc;             // sub-chunk bytes
     uint32_t ntiles, tiles_per_xcd, nslots;
     // batches: stripe s's nodes at data[i] + s * sdata, par[x] + s * spar (ntiles tiles per
-    // stripe, tiles_per_xcd over all nstripes * ntiles); nstripes = 0: one stripe
+    // stripe, tiles_per_xcd over all nstripes * ntiles); the host passes 1 for one stripe (0 is
+    // read as 1)
     uint32_t nstripes;
     int64_t sdata, spar;
     // SCRUB instantiations: result word of stripe 0 (stripe s ORs its mismatch bits into res[s]);

@@ -2,10 +2,7 @@
 // (repair_kernel.hpp), in their own translation unit; the host-side checks are in engine.hip.
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <set>
-#include <utility>
-
+#include "lds_attr.hpp"
 #include "repair_kernel.hpp"
 
 namespace clay {
@@ -54,20 +51,12 @@ static hipError_t launch_stream(const bs::RepArgs &a, hipStream_t stream, int de
     if (!force && nfull < uint64_t(8) * ns) return hipErrorNotSupported;  // under one tile per CU
     if (a.sc < 16) return hipErrorNotSupported;  // a partial tile reads whole 16-byte pieces
     if (a.sc * uint64_t(Kn::B::ALPHA) >= (uint64_t(1) << 32)) return hipErrorNotSupported;  // 32-bit row offsets
-    {
-        static std::mutex mu;
-        static std::set<int> done;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bs::k_bs_repair_stream<KD, M, Y0, PARTS, LOADERS>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(&bs::k_bs_repair_stream<KD, M, Y0, PARTS, LOADERS>),
+                                     Kn::LDS_BYTES, dev))
+        return e;
     bs::RepStreamArgs sa{};
     sa.r = a;
-    sa.region = uint32_t(((a.sc + 7) / 8 + 31) / 32 * 32);
+    sa.region = bs::xcd_region(a.sc);
     sa.ns = ns;
     bs::k_bs_repair_stream<KD, M, Y0, PARTS, LOADERS><<<dim3(ns * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(sa);
     const hipError_t e = hipGetLastError();

@@ -5,10 +5,8 @@
 // parity and compares where the encode stores.  And the compare-ending variant of the streaming
 // encode k_stream_encode (stream_encode.hpp) for (10,4,13), one stripe per launch and, with the
 // batched tile map (BATCH), many stripes in one.
-#include <mutex>
-#include <set>
-
 #include "bitslice_line.hpp"
+#include "lds_attr.hpp"
 #include "scrub_args.hpp"
 #include "stream_encode.hpp"
 
@@ -51,17 +49,7 @@ hipError_t launch_bs_scrub_kernel(int k, int m, bool bt, const bs::BsArgs &a, hi
 hipError_t launch_stream_scrub_kernel(const bs::BsArgs &a, hipStream_t stream, int dev) {
     using Kn = bs::StreamEnc<10, 4>;
     constexpr auto kern = &bs::k_stream_encode<10, 4, 0, bs::kStreamEncMap, true>;
-    static std::mutex mu;
-    static std::set<int> done;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(kern), Kn::LDS_BYTES, dev)) return e;
     kern<<<dim3(a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();
 }
@@ -71,17 +59,7 @@ hipError_t launch_stream_scrub_kernel(const bs::BsArgs &a, hipStream_t stream, i
 hipError_t launch_stream_scrub_batch_kernel(const bs::BsArgs &a, hipStream_t stream, int dev) {
     using Kn = bs::StreamEnc<10, 4>;
     constexpr auto kern = &bs::k_stream_encode<10, 4, 0, bs::kStreamEncMap, true, true>;
-    static std::mutex mu;
-    static std::set<int> done;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(kern), Kn::LDS_BYTES, dev)) return e;
     kern<<<dim3(8 * a.ntiles * a.nslots), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();
 }

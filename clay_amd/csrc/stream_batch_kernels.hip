@@ -4,10 +4,7 @@
 // (4 loader waves, lane map kStreamEncMap); only the tile map (BatchMap, stream_tile_map.hpp: tile
 // k of a workgroup belongs to stripe i(k)) and the stripe's offset in the SGPR base of every
 // access differ.
-#include <mutex>
-#include <set>
-#include <utility>
-
+#include "lds_attr.hpp"
 #include "stream_encode.hpp"
 
 namespace clay {
@@ -16,17 +13,7 @@ template <int KD>
 static hipError_t launch(const bs::BsArgs &a, hipStream_t stream, int dev) {
     using Kn = bs::StreamEnc<KD, 4>;
     constexpr auto kern = &bs::k_stream_encode<KD, 4, 0, bs::kStreamEncMap, false, true>;
-    static std::mutex mu;
-    static std::set<int> done;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!done.count(dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, Kn::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            done.insert(dev);
-        }
-    }
+    if (hipError_t e = lds_attr_once(reinterpret_cast<const void *>(kern), Kn::LDS_BYTES, dev)) return e;
     // a.ntiles groups of a.nslots workgroups per XCD
     kern<<<dim3(a.ntiles * a.nslots * 8), dim3(Kn::BLOCK), Kn::LDS_BYTES, stream>>>(a);
     return hipGetLastError();

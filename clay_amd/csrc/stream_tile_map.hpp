@@ -79,6 +79,21 @@ CLAY_TILE_MAP_HD inline uint32_t batch_groups(uint32_t per_xcd, uint32_t ns, uin
     return fit < n_stripes ? fit : n_stripes;
 }
 
+// The host's cut of a row of sc bytes over the 8 XCDs, for every kernel that streams XCD regions:
+// an XCD's region is sc / 8 rounded up to 32 bytes ...
+CLAY_TILE_MAP_HD inline uint32_t xcd_region(uint64_t sc) { return uint32_t(((sc + 7) / 8 + 31) / 32 * 32); }
+
+// ... and it gets one workgroup per tile of the region, at least one and at most per_xcd (one per
+// CU of the XCD).
+struct StreamCut {
+    uint32_t region, nslots;
+};
+CLAY_TILE_MAP_HD inline StreamCut stream_cut(uint64_t sc, uint32_t per_xcd, uint32_t tile = 256u) {
+    const uint32_t region = xcd_region(sc);
+    const uint32_t tiles = (region + tile - 1u) / tile > 1u ? (region + tile - 1u) / tile : 1u;
+    return {region, per_xcd < tiles ? per_xcd : tiles};
+}
+
 struct BatchMap {
     BalancedMap one;  // the cut of every stripe, for this workgroup's sub-slot
     uint32_t ns, sub, first, groups, count;

@@ -17,6 +17,7 @@
 using clay::bs::BalancedMap;
 using clay::bs::batch_groups;
 using clay::bs::BatchMap;
+using clay::bs::stream_cut;
 using clay::bs::StreamTile;
 
 static int failures = 0;
@@ -32,10 +33,6 @@ static int failures = 0;
         }                                      \
     } while (0)
 
-// the launch geometry of one stripe (launch_stream, engine.hip): region and workgroups per XCD
-static uint32_t region_of(uint32_t sc) { return ((sc + 7) / 8 + 31) / 32 * 32; }
-static uint32_t ns_of(uint32_t region, uint32_t per_xcd) { return std::min(per_xcd, std::max(1u, (region + 255u) / 256u)); }
-
 using Tile = std::array<uint32_t, 5>;  // xcd, sub-slot, round, b0, vend
 
 struct Shape {
@@ -44,7 +41,8 @@ struct Shape {
 };
 
 static Shape check(uint32_t sc, uint32_t n, uint32_t per_xcd) {
-    const uint32_t region = region_of(sc), ns = ns_of(region, per_xcd);
+    // the launch geometry of one stripe (stream_cut, as the engine launches it)
+    const uint32_t region = stream_cut(sc, per_xcd).region, ns = stream_cut(sc, per_xcd).nslots;
     const uint32_t G = batch_groups(per_xcd, ns, n);
     CHECK(G >= 1 && G <= n && (G * ns <= per_xcd || G == 1), "sc %u n %u per_xcd %u: %u groups of %u", sc, n, per_xcd, G, ns);
     // one stripe's cut, the reference

@@ -27,12 +27,10 @@ static int failures = 0;
         }                                      \
     } while (0)
 
-// the launch geometry of launch_stream (engine.hip): region and workgroups per XCD
-static uint32_t region_of(uint32_t sc) { return ((sc + 7) / 8 + 31) / 32 * 32; }
-
-// one (sc, ns): ns is the workgroup count per XCD the kernel is launched with
+// one (sc, ns): ns is the workgroup count per XCD the kernel is launched with (here swept, not
+// stream_cut's); the region is the engine's
 static void check(uint32_t sc, uint32_t ns, bool bench_shape) {
-    const uint32_t region = region_of(sc);
+    const uint32_t region = clay::bs::stream_cut(sc, ns).region;
     std::vector<std::pair<uint32_t, uint32_t>> tiles;  // all tiles of the row, (b0, vend)
     for (uint32_t xcd = 0; xcd < 8; xcd++) {
         const uint32_t x0 = xcd * region, x1 = std::min(x0 + region, sc);

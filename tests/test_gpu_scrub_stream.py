@@ -21,8 +21,8 @@ import pytest
 import clay_amd
 import scrub_sweeps as sw
 from clay_amd import ClayCode
+from stream_cut import dump_tiles
 from test_gpu_scrub import Stripes, _codeword, _expected, _oracle_parity, _places
-from test_scrub_stream_shapes_cpu import dump_tiles
 
 pytestmark = pytest.mark.gpu
 

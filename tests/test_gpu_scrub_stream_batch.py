@@ -27,9 +27,9 @@ import pytest
 import clay_amd
 import scrub_sweeps as sw
 from clay_amd import ClayCode
+from stream_cut import dump_tiles, xcd_region
 from test_gpu_scrub import Stripes, _codeword, _expected, _oracle_parity, _places
 from test_gpu_stream_batch import _per_xcd, _reference, batch_shape, case_shape
-from test_scrub_stream_shapes_cpu import dump_tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -315,8 +315,7 @@ def test_first_met_inside_a_capture(oracle_mod, torch_cuda, stream_batch):
 # 256-byte tiles per XCD over min(G, n) groups): (sc, n, inside) just inside and just outside on
 # each side, at the smallest stripe counts the rule allows
 def _fill_tiles(sc, n, per_xcd):
-    region = ((sc + 7) // 8 + 31) // 32 * 32
-    return batch_shape(sc, n, per_xcd)[1] * region / 256
+    return batch_shape(sc, n, per_xcd)[1] * xcd_region(sc) / 256
 
 
 def _auto_gate_case(torch, oracle_mod, sc, n, inside, cws):

@@ -32,6 +32,7 @@ import numpy as np
 import pytest
 
 from clay_amd import ClayCode, last_encode_path, last_launch_count, set_encode_path
+from stream_cut import batch_groups, stream_cut
 
 FILL = 0xA5
 GUARD = 4096
@@ -39,10 +40,10 @@ GUARD = 4096
 
 def batch_shape(sc, n, per_xcd):
     """(workgroups per stripe and XCD, groups per XCD, unlaunched slots per XCD, rounds of XCD 0,
-    stripes per group) as launch_stream_batch (engine.hip) and BatchMap cut a batch."""
-    region = ((sc + 7) // 8 + 31) // 32 * 32
-    ns = min(per_xcd, max(1, (region + 255) // 256))
-    groups = min(max(1, per_xcd // ns), n)
+    stripes per group) as launch_stream_batch (engine.hip: stream_cut, batch_groups) and BatchMap
+    cut a batch."""
+    region, ns = stream_cut(sc, per_xcd)
+    groups = batch_groups(per_xcd, ns, n)
     rounds = -(-min(region, sc) // (ns * 256))
     return ns, groups, max(0, per_xcd - groups * ns), rounds, [len(range(j, n, groups)) for j in range(groups)]
 

@@ -22,13 +22,13 @@ import numpy as np
 import pytest
 
 from clay_amd import ClayCode, set_encode_path, last_encode_path
+from stream_cut import stream_cut
 
 
 def layout(sc, ns_dev):
     """Per XCD: (workgroups, rounds, round widths, widths of the last round's tiles after clipping),
-    as launch_stream (engine.hip) and BalancedMap cut a row of sc bytes."""
-    region = ((sc + 7) // 8 + 31) // 32 * 32
-    ns = min(ns_dev, max(1, (region + 255) // 256))
+    as launch_stream (engine.hip: stream_cut) and BalancedMap cut a row of sc bytes."""
+    region, ns = stream_cut(sc, ns_dev)
     out = []
     for x in range(8):
         x0, x1 = x * region, min((x + 1) * region, sc)

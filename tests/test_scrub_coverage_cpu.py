@@ -12,8 +12,8 @@ import pytest
 
 import scrub_sweeps as sw
 from clay_amd import ClayCode
+from stream_cut import dump_tiles
 from test_gpu_scrub import TILE
-from test_scrub_stream_shapes_cpu import dump_tiles
 
 
 def _once(jj, pos, m, chunk):

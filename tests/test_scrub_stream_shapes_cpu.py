@@ -2,57 +2,29 @@
 
 tests/host/stream_tile_dump.cpp includes the tile map the kernel uses (stream_tile_map.hpp) and
 prints every workgroup's tiles; the XCD region and the workgroups per XCD are the host's
-arithmetic (engine.hip, launch_stream_scrub) restated here for 32 workgroups per XCD.  A tile is
+arithmetic (stream_cut, stream_tile_map.hpp) restated in tests/stream_cut.py, here for 32
+workgroups per XCD.  A tile is
 "ragged" when its width is no multiple of 16 (the plain compare path), "narrow" when it is below
 256 (lanes past its end masked off).
 """
-import os
-import shutil
-import subprocess
 from collections import Counter
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "stream_tile_dump.cpp")
-INC = os.path.join(ROOT, "clay_amd", "csrc")
+from stream_cut import dump_tiles, stream_cut
+
 SIZES = [16, 24, 264, 1064, 2048, 2288, 66176, 66184]
 PER_XCD = 32
 
 
-def _compiler():
-    for cxx in (os.environ.get("CXX"), "c++", "g++", "clang++", "/opt/rocm/lib/llvm/bin/clang++"):
-        if cxx and shutil.which(cxx):
-            return shutil.which(cxx)
-    pytest.fail("no C++ compiler found (set CXX)")
-
-
 def _launch_shape(sc):
-    region = ((sc + 7) // 8 + 31) // 32 * 32
-    return region, min(PER_XCD, max(1, (region + 255) // 256))
-
-
-def dump_tiles(workdir, sizes):
-    """sc -> list of (xcd, slot, round, b0, vend): stream_tile_dump compiled into `workdir` and run
-    on `sizes` (also the tile boundaries of the flip sweeps, tests/scrub_sweeps.py)."""
-    exe = os.path.join(str(workdir), "stream_tile_dump")
-    subprocess.run([_compiler(), "-std=c++17", "-O2", "-Wall", "-Werror", "-I", INC, "-o", exe, SRC], check=True)
-    args = []
-    for sc in sizes:
-        args += [str(sc), *map(str, _launch_shape(sc))]
-    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, check=True)
-    out = {sc: [] for sc in sizes}
-    for line in r.stdout.split("\n"):
-        if line:
-            sc, *t = map(int, line.split())
-            out[sc].append(tuple(t))
-    return out
+    return stream_cut(sc, PER_XCD)
 
 
 @pytest.fixture(scope="module")
 def tiles(tmp_path_factory):
     """sc -> list of (xcd, slot, round, b0, vend)"""
-    return dump_tiles(tmp_path_factory.mktemp("tiles"), SIZES)
+    return dump_tiles(tmp_path_factory.mktemp("tiles"), SIZES, PER_XCD)
 
 
 def _widths(ts, xcd=None, rnd=None):
