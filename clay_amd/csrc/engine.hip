@@ -36,6 +36,7 @@
 #include "repair_args.hpp"  // bit-sliced repair kernel: repair_kernel.hpp, instantiated in repair_stream.hip
 #include "repair_batch_map.hpp"  // its batch form's column map
 #include "decode_args.hpp"  // streaming-decode kernel: stream_decode.hpp, instantiated in decode_stream.hip
+#include "decode_pattern.hpp"  // host only: the kernel an erasure pattern runs on; the exec modes (kExec*)
 #include "line_args.hpp"  // line-local bit-sliced (4,2,5) encode / single-erasure decode: bitslice_line.hpp, in line_kernels.hip
 #include "scrub_args.hpp"  // compare-ending instantiations of the two bit-sliced encodes, in scrub_kernels.hip
 #include "kernels.hpp"
@@ -1273,11 +1274,9 @@ static int align_of(uintptr_t p) {
     return 1;
 }
 
-// Executor selection (clay_set_exec_mode): process-wide, read without locks.
+// Executor selection (clay_set_exec_mode; kExec*: decode_pattern.hpp): process-wide, read without locks.
 // Modes only choose kernels: every mode returns the reference's bytes on any input (4, the
 // retired single-launch decode, and 7, now the per-call clay_decode_device_codeword, are unused).
-enum : int { kExecAuto = 0, kExecGrouped = 1, kExecTile = 2, kExecStream = 3, kExecStreamLocal = 5,
-              kExecStreamFused2 = 6 };  // see clay_set_exec_mode
 static std::atomic<int> g_exec_mode{kExecAuto};
 static size_t tex_lds_budget() { return tuning().texec_lds; }
 // Lane width of the tile-fused executor for a plan (0 = not eligible): the widest of
@@ -2253,130 +2252,11 @@ static Error scrub_device_impl(const clay_code_t *code, StripeOperands data, Str
 // ---------------------------------------------------------------------------
 // Decode / repair on device
 // ---------------------------------------------------------------------------
-// The streaming decodes (stream_decode.hpp phase A + stream_local.hpp / stream_fused2.hpp) for
-// q = 4, t = 4 codes with k = 9 / 10.  `cin` / `cout`: internal node pointers (inputs of present
-// nodes, outputs of erased nodes, nullptr if not wanted).
-// Shared by the streaming decodes: pattern checks, RS rows used, H_K^-1, the v_perm tables of
-// its rows and of A_i = H_K^-1 gamma H_i, the node loads of a tile.  *ok = false: not eligible
-// (per_sec_max: the most erasures one y-section may hold).
-// Erasures per y-section of a q = 4, t = 4 code (`erased` per internal node)
-struct SectionErasures {
-    int per[4] = {0, 0, 0, 0};
-    int nsec = 0;  // sections with an erasure
-    int most = 0;  // the first section with the most erasures
-};
-static SectionErasures section_erasures(const std::vector<uint8_t> &erased) {
-    SectionErasures se;
-    for (size_t i = 0; i < 16 && i < erased.size(); i++) se.per[i / 4] += erased[i] ? 1 : 0;
-    for (int y = 0; y < 4; y++) {
-        if (se.per[y] > se.per[se.most]) se.most = y;
-        se.nsec += se.per[y] ? 1 : 0;
-    }
-    return se;
-}
-
-template <int KD>
-static Error dec_setup(CodeState &cs, const uint8_t *const *cin, uint8_t *const *cout, const std::vector<uint8_t> &erased,
-                       size_t sc, int per_sec_max, bs::DecArgs &a, std::vector<uint32_t> &tabs, bool *ok,
-                       bool any_sc = false) {
-    *ok = false;
-    const clay_code_t &c = cs.code;
-    using S = bs::Shape<KD, 4>;
-    if (int(c.k) != KD || c.m != 4 || c.q != 4 || c.t != 4 || c.q * c.t != 16) return Error{};
-    // any_sc (k_stream_local256: LDS-DMA and 16-byte stores at any byte alignment, partial pieces
-    // patched / stored byte by byte): any sub-chunk >= 512 and any chunk alignment; the other
-    // streaming decodes need 8-byte rows
-    if ((!any_sc && sc % 8) || sc < 512 || double(S::ALPHA) * double(sc) >= 4294967296.0) return Error{};
-    const GF &gf = GF::get();
-    std::vector<int> E;
-    for (int i = 0; i < 16; i++)
-        if (erased[i]) E.push_back(i);
-    if (E.empty() || E.size() > 4) return Error{};
-    const SectionErasures se = section_erasures(erased);
-    if (se.per[se.most] > per_sec_max) return Error{};
-    if (!any_sc && (misaligned8(cin, 16) || misaligned8(cout, 16))) return Error{};
-    if (Error e = rs_matches<S, 4>(cs)) return e;
-    a = bs::DecArgs{};
-    a.g2 = -1;
-    // RS rows used: the first 12 present shards (reconstruct, decode.rs:374); K = the rest
-    uint32_t used = 0;
-    int nused = 0;
-    std::vector<int> Kset;
-    for (int i = 0; i < 16; i++) {
-        if (!erased[i] && nused < S::K) {
-            used |= 1u << i;
-            nused++;
-        } else {
-            Kset.push_back(i);
-        }
-    }
-    if (nused != S::K || Kset.size() != 4) return Error{};
-    auto Hc = [&](int pchk, int i) -> uint8_t {
-        return i < S::K ? cs.rs.gen[(S::K + pchk) * S::K + i] : uint8_t(i - S::K == pchk ? 1 : 0);
-    };
-    std::vector<uint8_t> hk(16), hinv;
-    for (int pchk = 0; pchk < 4; pchk++)
-        for (int j = 0; j < 4; j++) hk[pchk * 4 + j] = Hc(pchk, Kset[j]);
-    if (!gf_invert(hk, 4, hinv)) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "singular RS check submatrix");
-    a.ne = uint32_t(E.size());
-    tabs.assign(bs::kDecTabWords, 0);
-    for (int i = 0; i < 16; i++) a.rix[i] = -1;
-    for (size_t r = 0; r < E.size(); r++) {
-        const int e = E[r];
-        a.rix[e] = int(r);
-        a.emask[e / 4] |= 1u << (e % 4);
-        a.out[r] = cout[e];
-        const int row = int(std::find(Kset.begin(), Kset.end(), e) - Kset.begin());
-        for (int j = 0; j < 4; j++) perm_table(hinv[row * 4 + j], &tabs[(r * 4 + j) * 8]);
-        for (int i = 0; i < 16; i++) {  // A_(y,x)[e_r] = (H_K^-1 gamma H_i)[row of e_r], i = 4y + x
-            uint8_t v = 0;
-            for (int j = 0; j < 4; j++) v ^= gf.mul(hinv[row * 4 + j], gf.mul(kGamma, Hc(j, i)));
-            perm_table(v, &tabs[(16 + i * 4 + r) * 8]);
-        }
-    }
-    a.used = used;
-    const uint32_t R = tuning().decode_ring;  // 10 unless a measurement sets CLAY_DECODE_RING
-    uint32_t n[4] = {0, 0, 0, 0}, nt = 0;
-    for (int y = 0; y < 4; y++) {
-        a.sec_off[y] = nt;
-        for (int x = 0; x < 4; x++) {
-            const int i = 4 * y + x;
-            a.node[i] = cin[i];
-            if (cin[i]) {
-                a.alive |= 1u << i;
-                a.load_node[nt++] = uint32_t(i);
-                n[y]++;
-            }
-        }
-    }
-    a.sec_off[4] = nt;
-    a.nt = nt;
-    // k_stream_fused2's compile-time phase-A copies: section y with at most one erased node x,
-    // every other node used and every node alive but that one and the shortened ones (i in [KD, 12))
-    for (int y = 0; y < 4; y++) {
-        uint32_t shortn = 0;
-        for (int x = 0; x < 4; x++)
-            if (4 * y + x >= KD && 4 * y + x < S::K) shortn |= 1u << x;
-        const uint32_t em = a.emask[y], un = (used >> (4 * y)) & 15u, al = (a.alive >> (4 * y)) & 15u;
-        const bool ok1 = __builtin_popcount(em) <= 1 && un == (~em & 15u) && al == (~em & ~shortn & 15u);
-        a.scase[y] = ok1 ? (em ? __builtin_ctz(em) : 4) : -1;
-        // k_stream_local256 (one erased row): no erasure, every node alive and only node 0 / nodes
-        // 0-1 used (the ignored nodes of one erasure: the last present ones); the fused decode
-        // takes the run-time copy for these
-        if (!ok1 && em == 0 && al == (~shortn & 15u) && (un == 1u || un == 3u)) a.scase[y] = un == 1u ? 5 : 6;
-    }
-    if (nt == 0) return Error{};
-    // the local kernel streams through R - 1 buffers (the last holds tables): a step's
-    // loads are issued during the step before it, across tiles too (section 3 -> section 0)
-    for (int y = 0; y < 4; y++)
-        if (n[y] > R - 1 || n[y] + n[(y + 1) % 4] > R - 1) return Error{};
-    if (R < 5) return Error{};  // S/C region (4 buffers) + the phase-B table buffer
-    a.ring = R;
-    a.sc = sc;
-    a.region = uint32_t(((sc + 7) / 8 + 63) / 64 * 64);
-    *ok = true;
-    return Error{};
-}
+// The streaming decodes (stream_decode.hpp phase A + stream_local.hpp / stream_local256.hpp /
+// stream_fused2.hpp) for q = 4, t = 4 codes with k = 9 / 10.  Which kernel an erasure pattern runs
+// on, and every kernel argument the pattern alone decides: decode_pattern.hpp.  Here, what needs
+// the code and the device: the RS rows used, H_K^-1, the v_perm tables, the pointers, the XCD cut
+// and the launch.
 
 // the pattern's tables: uploaded once per (table contents, device), cached with the code
 static Error dec_tables(CodeState &cs, const DevProps &prop, const std::vector<uint32_t> &tabs, hipStream_t stream,
@@ -2399,196 +2279,63 @@ hipError_t launch_stream_local_kernel(int kd, int g, const bs::DecArgs &a, hipSt
 hipError_t launch_stream_local256_kernel(int kd, int g, const bs::DecArgs &a, hipStream_t stream, int dev);  // decode_local256.hip
 hipError_t launch_stream_local256_any_kernel(int kd, int g, const bs::DecArgs &a, hipStream_t stream,
                                              int dev);  // decode_local256_any.hip
+hipError_t launch_stream_fused2_kernel(int kd, const bs::DecArgs &a, hipStream_t stream, int dev,
+                                       bool two);  // decode_stream.hip
 
-// Local decode (stream_local.hpp): erasures in one y-section G (any number) plus at most one
-// erasure in one other section g2 -- every iscore dependency inside a wave, one launch, no
-// workspace.  G = the section with the most erasures; section g2's digit goes to bits 0-1 of
-// the lane column.
+// One launch of the kernel `ch` names (bs::choose_decode, not DecKernel::None), no workspace.
+// `cin` / `cout`: internal node pointers (inputs of present nodes, outputs of erased nodes, nullptr
+// if not wanted).  Tables: t = r * 4 + j: row e_r of H_K^-1, check j; 16 + i * 4 + r: A_i[e_r] =
+// (H_K^-1 gamma H_i)[e_r]; kDecDetInv: (1 + gamma^2)^-1 for the kernels that invert both-erased pairs.
 template <int KD>
-static Error launch_stream_local(CodeState &cs, const DevProps &prop, const uint8_t *const *cin, uint8_t *const *cout,
-                                 const std::vector<uint8_t> &erased, size_t sc, hipStream_t stream, bool *done) {
-    *done = false;
-    const SectionErasures se = section_erasures(erased);
-    const int *per_sec = se.per, G = se.most;
-    if (se.nsec == 0 || se.nsec > 2) return Error{};
-    int g2 = -1;
-    for (int y = 0; y < 4; y++)
-        if (y != G && per_sec[y]) {
-            if (per_sec[y] > 1) return Error{};  // two sections with several erasures: rounds needed
-            g2 = y;
+static Error launch_stream_decode(CodeState &cs, const DevProps &prop, const uint8_t *const *cin, uint8_t *const *cout,
+                                  const bs::DecChoice &ch, size_t sc, hipStream_t stream) {
+    using S = bs::Shape<KD, 4>;
+    static_assert(S::K == bs::kDecK && S::ALPHA == 256, "the codes decode_pattern.hpp is written for");
+    if (Error e = rs_matches<S, 4>(cs)) return e;
+    const GF &gf = GF::get();
+    bs::DecArgs a = ch.a;
+    auto Hc = [&](int pchk, int i) -> uint8_t {
+        return i < S::K ? cs.rs.gen[(S::K + pchk) * S::K + i] : uint8_t(i - S::K == pchk ? 1 : 0);
+    };
+    std::vector<uint8_t> hk(16), hinv;
+    for (int pchk = 0; pchk < 4; pchk++)
+        for (int j = 0; j < 4; j++) hk[pchk * 4 + j] = Hc(pchk, ch.K[j]);
+    if (!gf_invert(hk, 4, hinv)) return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "singular RS check submatrix");
+    std::vector<uint32_t> tabs(bs::kDecTabWords, 0);
+    for (int e = 0; e < 16; e++) {
+        a.node[e] = cin[e];
+        if (a.rix[e] < 0) continue;
+        const int r = a.rix[e];
+        a.out[r] = cout[e];
+        const int row = int(std::find(ch.K, ch.K + 4, e) - ch.K);
+        for (int j = 0; j < 4; j++) perm_table(hinv[row * 4 + j], &tabs[(r * 4 + j) * 8]);
+        for (int i = 0; i < 16; i++) {  // A_(y,x)[e_r] = (H_K^-1 gamma H_i)[row of e_r], i = 4y + x
+            uint8_t v = 0;
+            for (int j = 0; j < 4; j++) v ^= gf.mul(hinv[row * 4 + j], gf.mul(kGamma, Hc(j, i)));
+            perm_table(v, &tabs[(16 + i * 4 + r) * 8]);
         }
-    // one erasure in section G plus at most one in g2, or two in G and none elsewhere: the
-    // 256-byte-run kernel (stream_local256.hpp), which also takes sub-chunks that are not a
-    // multiple of 8
-    const bool w256 = (per_sec[G] == 1 || (per_sec[G] == 2 && g2 < 0)) && !tuning().local_w64;
-    bs::DecArgs a;
-    std::vector<uint32_t> tabs;
-    bool ok = false;
-    Error e = dec_setup<KD>(cs, cin, cout, erased, sc, 4, a, tabs, &ok, w256);
-    if (e || !ok) return e;
-    // column digits: section g2 (if any) at bits 0-1, the others above in section order
-    {
-        uint32_t sh = 4;
-        for (int y = 0; y < 4; y++)
-            if (y != G) a.csh[y] = y == g2 ? 0u : (sh -= 2) + 2;
     }
-    a.g2 = g2;
-    if (g2 >= 0) a.x2 = uint32_t(__builtin_ctz(a.emask[g2]));
-    perm_table(gamma_det_inv(), &tabs[bs::kDecDetInv * 8]);  // (1 + gamma^2)^-1, transforms.rs:108-125
-    // the 256-byte-run kernel: XCD regions of whole 32-byte units and 256-byte tiles as the encode's
-    if (w256) {
+    const bool f2 = ch.kernel == bs::DecKernel::Fused2;
+    if (!f2 || a.npair) perm_table(gamma_det_inv(), &tabs[bs::kDecDetInv * 8]);  // transforms.rs:108-125
+    a.sc = sc;
+    if (ch.kernel == bs::DecKernel::Local256 || ch.kernel == bs::DecKernel::Local256Any) {
+        // XCD regions of whole 32-byte units and 256-byte tiles as the encode's
         const bs::StreamCut cut = bs::stream_cut(sc, prop.per_xcd());
         a.region = cut.region;
         a.nslots = cut.nslots;
     } else {
+        a.region = uint32_t(((sc + 7) / 8 + 63) / 64 * 64);
         a.nslots = std::min(prop.per_xcd(), std::max(1u, a.region / 64u));
     }
-    e = dec_tables(cs, prop, tabs, stream, &a.tabs);
-    if (e) return e;
-    if (w256) {
-        // rows of 8-byte multiples at 8-byte-aligned chunks: the 8-byte kernel; else the ANY one
-        const bool any = sc % 8 != 0 || misaligned8(cin, 16) || misaligned8(cout, 16);
-        if (any) CLAY_HIP(launch_stream_local256_any_kernel(KD, G, a, stream, prop.dev));
-        else CLAY_HIP(launch_stream_local256_kernel(KD, G, a, stream, prop.dev));
-        t_last_exec = "stream-local256";
-    } else {
-        CLAY_HIP(launch_stream_local_kernel(KD, G, a, stream, prop.dev));
-        t_last_exec = "stream-local";
+    if (Error e = dec_tables(cs, prop, tabs, stream, &a.tabs)) return e;
+    switch (ch.kernel) {
+        case bs::DecKernel::Local: CLAY_HIP(launch_stream_local_kernel(KD, ch.G, a, stream, prop.dev)); break;
+        case bs::DecKernel::Local256: CLAY_HIP(launch_stream_local256_kernel(KD, ch.G, a, stream, prop.dev)); break;
+        case bs::DecKernel::Local256Any: CLAY_HIP(launch_stream_local256_any_kernel(KD, ch.G, a, stream, prop.dev)); break;
+        default: CLAY_HIP(launch_stream_fused2_kernel(KD, a, stream, prop.dev, ch.two)); break;
     }
     t_last_launches += 1;
-    *done = true;
-    return Error{};
-}
-
-hipError_t launch_stream_fused2_kernel(int kd, const bs::DecArgs &a, hipStream_t stream, int dev,
-                                       bool two);  // decode_stream.hip
-
-// Rounds of k_stream_fused2 (stream_fused2.hpp): per section Y with an erasure and iscore level L,
-// the targets are the layers z with z_Y in E_Y and exactly L - 1 other sections y with z_y in E_y,
-// P(Y, L) = ceil(targets x 8 / 64) passes of 64 lanes x (8-byte piece).  The four loader waves share
-// them: each section with an erasure gets at least one wave, the spare waves go where they cut
-// the sum over levels of the busiest wave's passes most, and a section's nw waves take every
-// nw-th pass.  f2_plan packs, per loader wave li, byte li of a.lwave: bits 0-1 its section, 2-3 its
-// part, 4-5 nw - 1, bit 6 set (no section: 0); false when a wave would hold more than the kernel's
-// kF2Iters (TWO) / kF2Iters1 passes of some level.
-static uint32_t f2_targets(const uint32_t (&emask)[4], int Y, int L) {
-    uint32_t n = 0;
-    for (uint32_t z = 0; z < 256; z++) {
-        int red = 0;
-        bool ty = false;
-        for (int y = 0; y < 4; y++) {
-            const uint32_t d = (z >> (2 * (3 - y))) & 3u;
-            const bool in = (emask[y] >> d) & 1u;
-            red += in ? 1 : 0;
-            if (y == Y) ty = in;
-        }
-        n += (ty && red == L) ? 1u : 0u;
-    }
-    return n;
-}
-static bool f2_plan(const uint32_t (&emask)[4], bool two, uint32_t *lwave) {
-    uint32_t P[4][4] = {}, nw[4] = {};
-    int nact = 0;
-    for (int Y = 0; Y < 4; Y++) {
-        if (!emask[Y]) continue;
-        nact++;
-        nw[Y] = 1;
-        for (int L = 1; L <= 4; L++) P[Y][L - 1] = (f2_targets(emask, Y, L) * 8u + 63u) / 64u;
-    }
-    const int *cap = two ? bs::kF2Iters : bs::kF2Iters1;
-    // the spare waves: the split (every active section >= 1 wave, 4 in all) with the smallest sum
-    // over levels of the busiest wave's passes (each level's round is one step) among those within
-    // the kernel's item registers, first in lexicographic order of (nw[0], .., nw[3]) among equals
-    if (nact > 0 && nact < 4) {
-        uint32_t best[4] = {0, 0, 0, 0}, bcost = ~0u;
-        for (uint32_t n0 = 0; n0 <= 4; n0++)
-            for (uint32_t n1 = 0; n1 <= 4; n1++)
-                for (uint32_t n2 = 0; n2 <= 4; n2++)
-                    for (uint32_t n3 = 0; n3 <= 4; n3++) {
-                        const uint32_t n[4] = {n0, n1, n2, n3};
-                        if (n0 + n1 + n2 + n3 != 4) continue;
-                        bool ok = true;
-                        for (int Y = 0; Y < 4; Y++) ok = ok && ((n[Y] > 0) == (nw[Y] > 0));
-                        if (!ok) continue;
-                        uint32_t cost = 0;
-                        for (int L = 0; L < 4; L++) {
-                            uint32_t mx = 0;
-                            for (int Y = 0; Y < 4; Y++)
-                                if (n[Y]) mx = std::max(mx, (P[Y][L] + n[Y] - 1u) / n[Y]);
-                            if (mx > uint32_t(cap[L])) ok = false;  // over the kernel's item registers
-                            cost += mx;
-                        }
-                        if (!ok) continue;
-                        if (cost < bcost) {
-                            bcost = cost;
-                            for (int Y = 0; Y < 4; Y++) best[Y] = n[Y];
-                        }
-                    }
-        if (bcost == ~0u) return false;  // no split within the item registers
-        for (int Y = 0; Y < 4; Y++) nw[Y] = best[Y];
-    }
-    uint32_t pack = 0;
-    int li = 0;
-    for (int Y = 0; Y < 4; Y++) {
-        for (uint32_t part = 0; part < nw[Y]; part++, li++)
-            pack |= (uint32_t(Y) | part << 2 | (nw[Y] - 1u) << 4 | 64u) << (8 * li);
-        for (int L = 0; L < 4 && nw[Y]; L++)
-            if ((P[Y][L] + nw[Y] - 1u) / nw[Y] > uint32_t(cap[L])) return false;
-        if (two && P[Y][3]) return false;  // the TWO kernel inverts the pairs during the level-4 round's slot
-    }
-    *lwave = pack;
-    return true;
-}
-
-// Fused decode v2 (stream_fused2.hpp): erasures in at least two y-sections with at most two per
-// section (round 6: two in a section -- both-erased PFT pairs inverted after the rounds), one launch,
-// rounds of tile k-1 on the loader waves while tile k streams.  Ring of 10 - ne node buffers + the
-// S/C region.
-template <int KD>
-static Error launch_stream_fused2(CodeState &cs, const DevProps &prop, const uint8_t *const *cin, uint8_t *const *cout,
-                                  const std::vector<uint8_t> &erased, size_t sc, hipStream_t stream, bool *done) {
-    *done = false;
-    bs::DecArgs a;
-    std::vector<uint32_t> tabs;
-    bool ok = false;
-    Error e = dec_setup<KD>(cs, cin, cout, erased, sc, 2, a, tabs, &ok);
-    if (e || !ok) return e;
-    if (a.ne < 2) return Error{};
-    bool two = false;
-    for (int y = 0; y < 4; y++) two = two || __builtin_popcount(a.emask[y]) > 1;
-    if (!f2_plan(a.emask, two, &a.lwave)) return Error{};  // more round targets than the kernel's item registers
-    // both-erased pairs: per erased row, the other erased row of its section
-    a.npair = 0;
-    for (int r = 0; r < 4; r++) a.pinfo[r] = 0;
-    for (int y = 0; y < 4; y++) {
-        if (__builtin_popcount(a.emask[y]) != 2) continue;
-        const uint32_t x1 = uint32_t(__builtin_ctz(a.emask[y])), x2 = 31u - uint32_t(__builtin_clz(a.emask[y]));
-        const int r1 = a.rix[4 * y + int(x1)], r2 = a.rix[4 * y + int(x2)];
-        a.pinfo[r1] = 1u | uint32_t(r2) << 1 | uint32_t(y) << 3 | x1 << 5 | x2 << 7;
-        a.pinfo[r2] = 1u | uint32_t(r1) << 1 | uint32_t(y) << 3 | x2 << 5 | x1 << 7;
-        a.npair += 2;
-    }
-    if (a.npair) perm_table(gamma_det_inv(), &tabs[bs::kDecDetInv * 8]);  // (1 + gamma^2)^-1
-    const uint32_t RB = 10 - a.ne;  // the S/C region takes ne of the 10 node buffers of LDS
-    // the loads of a step are issued during the step before it when the ring holds both; else
-    // (round 6: two neighbouring sections with 7-8 alive nodes and RB = 6) the step is split: the
-    // rest of its loads after its barrier, behind a second one.  Section 0 of tile k + 1 needs no
-    // split: every ring buffer is free at B_r(k), before its barrier.
-    a.split = 0;
-    for (int y = 0; y < 4; y++) {
-        const uint32_t ny = a.sec_off[y + 1] - a.sec_off[y];
-        if (ny > RB) return Error{};
-        if (y > 0 && (a.sec_off[y] - a.sec_off[y - 1]) + ny > RB) a.split |= 1u << y;
-    }
-    a.ring = RB;
-    a.nslots = std::min(prop.per_xcd(), std::max(1u, a.region / 64u));
-    e = dec_tables(cs, prop, tabs, stream, &a.tabs);
-    if (e) return e;
-    if (!two) a.split = 0;  // (no pattern with one erasure per section overflows the ring)
-    CLAY_HIP(launch_stream_fused2_kernel(KD, a, stream, prop.dev, two));
-    t_last_launches += 1;
-    t_last_exec = "stream-fused2";
-    *done = true;
+    t_last_exec = f2 ? "stream-fused2" : ch.kernel == bs::DecKernel::Local ? "stream-local" : "stream-local256";
     return Error{};
 }
 
@@ -2764,49 +2511,28 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
                               &done);
         if (e || done) return e;
     }
-    // streaming decodes of q = 4, t = 4 codes (sc % 8 == 0, sc >= 512):
-    //  * the local decode (erasures in one section plus at most one other, stream_local.hpp):
-    //    auto, "stream" and "stream-local";
-    //  * the fused decode v2 (2-4 erasures in distinct sections, stream_fused2.hpp): auto from 3
-    //    erasures, "stream" and "stream-fused2" from 2 ((10,4,13) 1 GiB: {0,4,8,12} 0.52 ms vs 0.92
-    //    on the grouped executor, {0,4,8} 0.48 vs 0.79; {0,4} 0.458 vs 0.452 on the local decode;
-    //    profiles/r04/fused2/)
-    const bool stream_all = xmode == kExecStream;
-    const bool try_local = xmode == kExecAuto || stream_all || xmode == kExecStreamLocal;
-    const bool try_f2 = xmode == kExecStreamFused2 || stream_all || (xmode == kExecAuto && n_erased >= 3);
-    // (2,1) sections (two erasures in one section, one in another): the fused decode v2 first --
-    // 0.48-0.53 ms vs 0.50-0.54 on the 64-byte local decode (profiles/r06/decode/two_small_*)
-    bool f2_first = false;
-    if (try_f2 && try_local && n_erased == 3 && tn == 16) {
-        const SectionErasures se = section_erasures(erased);
-        f2_first = se.nsec == 2 && se.per[se.most] == 2;
-    }
-    if ((try_local || try_f2) && tn == 16) {
+    // streaming decodes of q = 4, t = 4 codes with k = 9 / 10: the kernel bs::choose_decode names
+    if (tn == 16 && c.m == 4 && c.q == 4 && c.t == 4 && (c.k == 9 || c.k == 10)) {
         const uint8_t *cin[16] = {};
         uint8_t *cout[16] = {};
+        uint32_t gone = 0, alive = 0;
         for (size_t i = 0; i < c.n; i++) {
             const size_t in = internal_of(c, i);
             if (erased[in]) cout[in] = want[in] ? outs[i] : nullptr;
             else cin[in] = chunks[i];
         }
-        bool done = false;
-        const DevProps &prop = dev_props(dev);
+        for (size_t in = 0; in < 16; in++) {
+            gone |= erased[in] ? 1u << in : 0u;
+            alive |= cin[in] ? 1u << in : 0u;
+        }
         const size_t sc = chunk / c.sub_chunk_no;
         hipStream_t st = static_cast<hipStream_t>(stream);
-        auto fused2 = [&] {
-            return c.k == 10 ? launch_stream_fused2<10>(cs, prop, cin, cout, erased, sc, st, &done)
-                 : c.k == 9  ? launch_stream_fused2<9>(cs, prop, cin, cout, erased, sc, st, &done)
-                             : Error{};
-        };
-        if (f2_first) e = fused2();
-        if (e || done) return e;
-        if (try_local) {
-            if (c.k == 10) e = launch_stream_local<10>(cs, prop, cin, cout, erased, sc, st, &done);
-            else if (c.k == 9) e = launch_stream_local<9>(cs, prop, cin, cout, erased, sc, st, &done);
-            if (e || done) return e;
-        }
-        if (try_f2 && !f2_first) e = fused2();
-        if (e || done) return e;
+        const bs::DecChoice ch =
+            bs::choose_decode(int(c.k), gone, alive, xmode, sc, !misaligned8(cin, 16) && !misaligned8(cout, 16),
+                              tuning().decode_ring, tuning().local_w64);
+        if (ch.kernel != bs::DecKernel::None)
+            return c.k == 10 ? launch_stream_decode<10>(cs, dev_props(dev), cin, cout, ch, sc, st)
+                             : launch_stream_decode<9>(cs, dev_props(dev), cin, cout, ch, sc, st);
     }
     return run_plan(cs, *plan, dev, *ds, static_cast<hipStream_t>(stream), P, chunk / c.sub_chunk_no, chunk);
 }

@@ -492,12 +492,14 @@ int clay_set_encode_path(int mode);
  *                the pattern (the (2,1) patterns: the fused decode v2 first), else the fused
  *                decode v2 (2-4 erasures, at most two per section); everything else as auto
  *   5 stream-local -- every decode a local kernel takes on it ("stream-local256" /
- *                "stream-local"); else as auto
+ *                "stream-local", the (2,1) patterns included); every other decode on auto's
+ *                plan executors (no fused decode v2, no k_bs_decode1)
  *   6 stream-fused2 -- decodes of 2-4 erasures with at most two per y-section on the fused
  *                decode v2 (k_stream_fused2, "stream-fused2"; ring of 10 - e node buffers: a
  *                section's surviving real nodes fit it, two neighbouring sections that do not
  *                run as a split step; the loader waves' round items fit their registers);
- *                else as auto
+ *                every other decode, one erasure included, on auto's plan executors (no local
+ *                decode, no k_bs_decode1)
  * (4 and 7 are retired: the single-launch decode of round 3 and the process-wide "codeword"
  * mode, now the per-call clay_decode_device_codeword.)
  * No CLAY_* environment variable is read on a call path; the measurement knobs (planner and

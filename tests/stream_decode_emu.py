@@ -12,6 +12,8 @@ The kernels themselves are checked on the GPU (tests/test_gpu_stream_local.py,
 tests/test_gpu_stream_decode.py)."""
 import numpy as np
 
+from decode_pattern import local_eligible  # noqa: F401  (the patterns local_decode takes)
+
 POLY = 0x11D
 GAMMA = 2
 
@@ -193,14 +195,6 @@ def presolved_by_source(code, C, E, used, rows, A, G):
                 for r in range(len(E)):
                     V[r, zt] ^= gmul(A[4 * G + b][r], C[src, z])
     return V
-
-
-def local_eligible(code, erased_ext):
-    per = [0] * 4
-    for e in erased_ext:
-        per[code.internal(e) // 4] += 1
-    nz = sorted([p for p in per if p], reverse=True)
-    return 1 <= len(erased_ext) <= 4 and len(nz) <= 2 and (len(nz) < 2 or nz[1] == 1)
 
 
 def local_decode(code, chunks, erased_ext):

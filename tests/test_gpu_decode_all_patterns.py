@@ -3,14 +3,14 @@ parity outputs against the oracle on non-codeword input.
 
 Decode is where the erasure pattern changes the path: every pattern has its own cached plan
 (plan.cpp), the streaming kernels a per-pattern device table, and k_stream_fused2 a per-pattern
-loader-wave split, ring and split-step choice (engine.hip f2_plan / launch_stream_fused2).  The
+loader-wave split, ring and split-step choice (decode_pattern.hpp f2_plan / fused2_shape).  The
 other decode tests sample the 3- and 4-erasure patterns; here none is left out.
 
  * streaming codes ((10,4,13), (9,4,12)) at sc = 520 -- eight full 64-byte tiles (two 256-byte runs)
    plus an 8-byte ragged tail, the smallest size at which every pattern meets both the full-tile
    and the tail code of the streaming kernels (sc >= 512, sc % 8 == 0): exec modes "auto",
    "stream-local" and "stream-fused2", the kernel that ran asserted per mode from the predicates of
-   test_gpu_stream_decode.py;
+   tests/decode_pattern.py;
  * every code at sc = 22 (one 16-byte piece, one 4-byte piece, a 2-byte tail; below 512, so no
    streaming kernel applies): the plan executors, "grouped" and "tile".
 
@@ -34,9 +34,9 @@ import pytest
 
 import clay_amd
 from clay_amd import ClayCode
+from decode_pattern import fused2_eligible, local_eligible, stream_path
 from test_gpu_batch_repair import FILL, GUARD, guarded
 from test_gpu_parity import CONFIGS as PARITY_CONFIGS
-from test_gpu_stream_decode import fused2_eligible, local_eligible, stream_path
 
 STREAM_CONFIGS = [(10, 4, 13), (9, 4, 12)]
 PLAN_CONFIGS = PARITY_CONFIGS + [(9, 4, 12)]
@@ -55,7 +55,7 @@ def n_patterns(cfg):
 
 # Slices patterns[j::S] of a code's pattern list, one parametrized case each, at most 200 patterns
 # a case: 8 slices for (10,4,13), 6 for (9,4,12), 4 for (8,4,11), 3 for (7,4,9), 2 for (9,3,11).
-# A streaming case is the slower kind (four decodes, two plans and ~12 ms of path predicates in
+# A streaming case is the slower kind (four decodes, two plans and the path predicates in
 # Python per pattern): 1.6 s measured for the slowest one, 0.3 s for the slowest plan-executor case.
 STREAM_SLICES = {cfg: -(-n_patterns(cfg) // 200) for cfg in STREAM_CONFIGS}
 PLAN_SLICES = {cfg: -(-n_patterns(cfg) // 200) for cfg in PLAN_CONFIGS}

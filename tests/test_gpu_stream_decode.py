@@ -13,53 +13,9 @@ import pytest
 
 import clay_amd
 from clay_amd import ClayCode
+from decode_pattern import fused2_eligible, local_eligible, patterns, per_section, stream_path
 
 pytestmark = pytest.mark.gpu
-
-
-def _internal(c, e):
-    return e if e < c.k else e + c.nu
-
-
-def stream_eligible(c, er):
-    per = [0] * c.t
-    for e in er:
-        per[_internal(c, e) // c.q] += 1
-    return len(er) >= 1 and max(per) <= 1
-
-
-def _patterns(c, seed, n3, n4):
-    pats = [list(e) for r in (1, 2) for e in itertools.combinations(range(c.n), r)]
-    rng = np.random.default_rng(seed)
-    for r, cnt in ((3, n3), (4, n4)):
-        allp = [list(e) for e in itertools.combinations(range(c.n), r)]
-        for i in rng.permutation(len(allp))[:cnt]:
-            pats.append(allp[i])
-    return pats
-
-
-def local_eligible(c, er):
-    """k_stream_local: erasures in one y-section plus at most one erasure in one other section."""
-    per = [0] * c.t
-    for e in er:
-        per[_internal(c, e) // c.q] += 1
-    busy = [n for n in per if n]
-    return len(busy) == 1 or (len(busy) == 2 and min(busy) == 1)
-
-
-def stream_path(c, er):
-    """The kernel exec mode "stream" runs a pattern on (None: the plan executor)."""
-    per = sorted((sum(1 for e in er if _internal(c, e) // c.q == y) for y in range(c.t)), reverse=True)
-    if len(er) == 3 and per[:2] == [2, 1] and fused2_eligible(c, er, two=True):
-        return "stream-fused2"  # (2,1) sections: the fused decode v2 first (round 6)
-    if local_eligible(c, er):
-        per = [0] * c.t
-        for e in er:
-            per[_internal(c, e) // c.q] += 1
-        return "stream-local256" if max(per) == 1 or [n for n in per if n] == [2] else "stream-local"
-    if fused2_eligible(c, er, two=True):
-        return "stream-fused2"
-    return None
 
 
 @pytest.fixture
@@ -98,7 +54,7 @@ def test_stream_decode_patterns_random_inputs(oracle_mod, torch_cuda, stream_mod
     chunk = c.sub_chunk_no * sc
     rng = np.random.default_rng(sc + cfg[0])
     n_stream = 0
-    for er in _patterns(c, sc, 24, 40):
+    for er in patterns(c, sc, 24, 40):
         chunks = rng.integers(0, 256, (c.n, chunk), dtype=np.uint8)
         got = _decode_dev(torch, c, chunks, er, chunk, want_parity=False)
         path = clay_amd.last_exec_path()
@@ -125,7 +81,7 @@ def test_stream_decode_codeword_incl_parity(oracle_mod, torch_cuda, stream_mode,
     chunk = c.sub_chunk_no * sc
     ref = o.encode_array(np.random.default_rng(sc).integers(0, 256, c.k * chunk, dtype=np.uint8))
     pats = [[0, 4, 8, 12]] if cfg == (10, 4, 13) else [[0, 4, 8, 11]]
-    pats += [p for p in _patterns(c, 5, 12, 12) if stream_path(c, p)]
+    pats += [p for p in patterns(c, 5, 12, 12) if stream_path(c, p)]
     for er in pats:
         got = _decode_dev(torch, c, ref, er, chunk)
         assert clay_amd.last_exec_path() == stream_path(c, er), er
@@ -150,61 +106,6 @@ def test_stream_decode_matches_grouped_executor(oracle_mod, torch_cuda, stream_m
     clay_amd.set_exec_mode("stream")
     for e in er:
         assert np.array_equal(a[e], b[e]), e
-
-
-def f2_fits(c, er, two=False):
-    """The host's round-capacity check (engine.hip f2_plan): per section Y with an erasure and
-    iscore level L, P(Y, L) = passes of 64 lanes x 8-byte pieces over the layers with z_Y in E_Y
-    and L erased sections red; the four loader waves: at least one per section with an erasure,
-    split to minimise the sum over levels of the busiest wave's passes; a wave holds <= kF2Iters
-    (two) / kF2Iters1 passes per level."""
-    iters = [5, 4, 2, 1] if two else [6, 4, 2, 1]
-    em = [0] * c.t
-    for e in er:
-        i = _internal(c, e)
-        em[i // c.q] |= 1 << (i % c.q)
-    P = {}
-    for Y in range(c.t):
-        if not em[Y]:
-            continue
-        for L in range(1, 5):
-            n = 0
-            for z in range(256):
-                d = [(z >> (2 * (3 - y))) & 3 for y in range(4)]
-                red = sum(1 for y in range(4) if (em[y] >> d[y]) & 1)
-                n += 1 if (em[Y] >> d[Y]) & 1 and red == L else 0
-            P[Y, L] = (n * 8 + 63) // 64
-    act = [y for y in range(c.t) if em[y]]
-    best, bcost = None, None
-    for n in itertools.product(range(5), repeat=4):  # lexicographic, as the host's loops
-        if sum(n) != 4 or any((n[y] > 0) != (y in act) for y in range(4)):
-            continue
-        mx = [max(-(-P[y, L] // n[y]) for y in act) for L in range(1, 5)]
-        if any(m > iters[L] for L, m in enumerate(mx)):
-            continue
-        cost = sum(mx)
-        if bcost is None or cost < bcost:
-            best, bcost = n, cost
-    return best is not None
-
-
-def fused2_eligible(c, er, two=False):
-    """k_stream_fused2: 2-4 erasures in distinct y-sections (two=True: at most two per section,
-    round 6) whose round targets fit the kernel's item registers, and a ring of 10 - e node buffers
-    that holds any two neighbouring sections' surviving real nodes."""
-    per = [0] * c.t
-    for e in er:
-        per[_internal(c, e) // c.q] += 1
-    if not 2 <= len(er) <= c.t or max(per) > (2 if two else 1) or not f2_fits(c, er, two):
-        return False
-    alive = [0] * c.t
-    for i in range(c.n):
-        if i not in er:
-            alive[_internal(c, i) // c.q] += 1
-    rb = 10 - len(er)
-    if two:  # round 6: neighbouring sections beyond the ring run as split steps
-        return max(alive) <= rb
-    return all(alive[y] + alive[(y + 1) % c.t] <= rb for y in range(c.t))  # incl. section 3 -> next tile's 0
 
 
 @pytest.mark.parametrize("cfg", [(10, 4, 13), (9, 4, 12)])
@@ -271,9 +172,7 @@ def _two_in_a_section(c, r=4):
     (2,2) sections), which round 6 moved from the grouped executor to k_stream_fused2."""
     out = []
     for er in itertools.combinations(range(c.n), r):
-        per = [0] * c.t
-        for e in er:
-            per[_internal(c, e) // c.q] += 1
+        per = per_section(c, er)
         if max(per) == 2 and not local_eligible(c, list(er)) and fused2_eligible(c, list(er), two=True):
             out.append(list(er))
     return out

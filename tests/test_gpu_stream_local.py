@@ -15,43 +15,9 @@ import pytest
 
 import clay_amd
 from clay_amd import ClayCode
+from decode_pattern import local_eligible, local_path, patterns
 
 pytestmark = pytest.mark.gpu
-
-
-def _internal(c, e):
-    return e if e < c.k else e + c.nu
-
-
-def local_eligible(c, er):
-    per = [0] * c.t
-    for e in er:
-        per[_internal(c, e) // c.q] += 1
-    nz = sorted([p for p in per if p], reverse=True)
-    return 1 <= len(er) <= c.m and len(nz) <= 2 and (len(nz) < 2 or nz[1] == 1)
-
-
-def local_path(c, er, mode="stream-local"):
-    """The kernel a local-eligible pattern runs on (8-byte rows, sc >= 512): in auto, the (2,1)
-    patterns take the fused decode v2 first (round 6; every one of them fits it for (10,4,13) and
-    (9,4,12), tests/test_gpu_stream_decode.py::fused2_eligible)."""
-    per = [0] * c.t
-    for e in er:
-        per[_internal(c, e) // c.q] += 1
-    busy = [n for n in per if n]
-    if mode == "auto" and len(er) == 3 and sorted(busy) == [1, 2]:
-        return "stream-fused2"
-    return "stream-local256" if max(per) == 1 or busy == [2] else "stream-local"
-
-
-def _local_patterns(c, seed, n3, n4):
-    pats = [list(e) for r in (1, 2) for e in itertools.combinations(range(c.n), r)]
-    rng = np.random.default_rng(seed)
-    for r, cnt in ((3, n3), (4, n4)):
-        allp = [list(e) for e in itertools.combinations(range(c.n), r) if local_eligible(c, list(e))]
-        for i in rng.permutation(len(allp))[:cnt]:
-            pats.append(allp[i])
-    return pats
 
 
 @pytest.fixture(params=["stream-local", "auto"])
@@ -81,7 +47,7 @@ def test_local_decode_random_inputs(oracle_mod, torch_cuda, local_mode, cfg, sc)
     chunk = c.sub_chunk_no * sc
     rng = np.random.default_rng(sc + 7 * cfg[0])
     n_local = 0
-    for er in _local_patterns(c, sc, 16, 16):
+    for er in patterns(c, sc, 16, 16, local_eligible):
         chunks = rng.integers(0, 256, (c.n, chunk), dtype=np.uint8)
         got = _decode_dev(torch, c, chunks, er, chunk, want_parity=False)
         path = clay_amd.last_exec_path()
@@ -108,7 +74,7 @@ def test_local_decode_codeword_incl_parity(oracle_mod, torch_cuda, local_mode, c
     chunk = c.sub_chunk_no * sc
     ref = o.encode_array(np.random.default_rng(sc).integers(0, 256, c.k * chunk, dtype=np.uint8))
     pats = [[0], [0, 4], [0, 1], [0, 1, 4], [0, 1, 2, 3], [c.n - 1], [c.n - 2, c.n - 1], [0, c.n - 1]]
-    pats += [p for p in _local_patterns(c, 3, 10, 10) if local_eligible(c, p)][::5]
+    pats += [p for p in patterns(c, 3, 10, 10, local_eligible) if local_eligible(c, p)][::5]
     for er in pats:
         assert local_eligible(c, er), er
         got = _decode_dev(torch, c, ref, er, chunk)
