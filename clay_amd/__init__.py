@@ -28,7 +28,7 @@ __all__ = [
     "InsufficientHelperData", "InconsistentChunkSizes", "TooManyErasures",
     "ReconstructionFailed", "MissingYSectionHelper", "Overflow", "DeviceError",
     "set_encode_path", "last_encode_path", "last_launch_count", "set_exec_mode", "last_exec_path",
-    "set_scrub_path",
+    "set_scrub_path", "DECODE_STREAM_BATCH_AUTO_MAX_SC",
 ]
 
 
@@ -116,6 +116,14 @@ def set_encode_path(mode: str, tile: int = 0) -> str:
 
 _EXEC_MODES = {"auto": 0, "grouped": 1, "tile": 2, "stream": 3, "stream-local": 5, "stream-fused2": 6}
 
+# Exec mode 'auto' and the one-launch streaming decode batch ('stream-local256-batch', see
+# ClayCode.decode_device_strided): the largest sub-chunk, in bytes, up to which 'auto' takes it for
+# stripes of more than 4 MiB of data (0 would mean never): the largest swept sub-chunk up to which
+# the batch was no slower than the per-stripe loop in every cell of the sweep
+# (profiles/r14/batch_decode_stream_gate.txt).  Restates kDecodeStreamBatchMaxSc of csrc/engine.hip
+# (tests/test_local256_batch_gate_cpu.py compares the two).
+DECODE_STREAM_BATCH_AUTO_MAX_SC = 262152
+
 
 def set_exec_mode(mode: str) -> str:
     """Process-wide plan executor for decode / repair / staged encode (clay.h): 'auto' (tile-fused
@@ -126,7 +134,13 @@ def set_exec_mode(mode: str) -> str:
     'grouped' (one launch per level; batched decodes and repairs 'grouped-batch'), 'tile',
     'stream' (every decode a streaming kernel takes:
     local, else fused v2 from 2 erasures; the streaming repair kernel at any sub-chunk size),
-    'stream-local' or 'stream-fused2' (that kernel wherever it applies).  Modes choose kernels
+    'stream-local' or 'stream-fused2' (that kernel wherever it applies).  Batched decodes of
+    (10,4,13) whose pattern runs on the 256-byte-run local decode (decode_device_strided lists the
+    conditions) are ONE launch of its batch variant ('stream-local256-batch') under 'stream' at any
+    eligible size; under 'auto' only for stripes of more than 4 MiB of data with sub-chunks up to
+    DECODE_STREAM_BATCH_AUTO_MAX_SC = 262,152 bytes (the measured gate of clay.h);
+    'stream-local' keeps one launch per stripe ('stream-local256', the A/B partner), 'grouped' /
+    'tile' never take it and 'stream-fused2' is unchanged.  Modes choose kernels
     only: every mode returns the reference's bytes on any input.  The scrub of (4,2,5) runs the
     line kernel ('bs-scrub1') except under 'grouped' / 'tile', which keep the v1 kernel
     ('bs-scrub') for A/B.  The scrub of (10,4,13) on 8-byte rows (sub-chunk a multiple of 8 and at
@@ -170,7 +184,8 @@ def set_scrub_path(name: str) -> str:
 def last_exec_path() -> str:
     """Plan executor of this thread's last decode / repair / staged encode: 'tile' | 'grouped' |
     'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
-    'bs-decode1-batch' (the batched decodes) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
+    'bs-decode1-batch' / 'stream-local256-batch' (the batched decodes in one launch: (4,2,5) on the line
+    kernel, (10,4,13) on the 256-byte-run local decode) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
     (both) | the scrubs' 'bs-scrub1' / 'bs-scrub' (one launch per stripe), 'bs-scrub1-batch' /
     'bs-scrub-batch' (a batch in one launch), 'stream-scrub' ((10,4,13) on the streaming kernel:
     one launch per stripe in every entry point) and 'stream-scrub-batch' (many stripes in one
@@ -488,7 +503,18 @@ class ClayCode:
         """Batched decode of stripes with the same erasure set at fixed strides (clay.h
         clay_decode_device_strided): every erased node e of stripe s is rebuilt at
         out + s * out_stripe_stride + e * out_node_stride; out may be chunks (in place).
-        Strides default to a contiguous [n_stripes][n][chunk_size] layout."""
+        Strides default to a contiguous [n_stripes][n][chunk_size] layout.
+
+        The streaming batch ('stream-local256-batch', last_launch_count 1 for any number of
+        stripes): a call is eligible when the code is (10,4,13), n_stripes >= 2, the pattern runs on
+        the 256-byte-run local decode on 8-byte rows (every 1-erasure and 2-erasure pattern; a
+        sub-chunk that is a multiple of 8 with 512 <= sub-chunk < 2^24; chunks 8-byte aligned) and
+        both stripe strides are multiples of 8.  Exec mode 'stream' takes every eligible call,
+        stripes of 4 MiB or less included ('grouped-batch' otherwise); 'auto' only stripes of more
+        than 4 MiB of data with sub-chunks up to DECODE_STREAM_BATCH_AUTO_MAX_SC = 262,152 bytes;
+        'stream-local' (one launch per stripe, the A/B partner), 'grouped' and 'tile' never;
+        'stream-fused2' is unchanged.  Anything not eligible runs as before.  Inside a stream
+        capture the call needs one warm call of the same pattern first (its table upload)."""
         ns_ = node_stride or chunk_size
         ss_ = stripe_stride or self.n * chunk_size
         ons = out_node_stride or chunk_size
@@ -506,7 +532,10 @@ class ClayCode:
                             device: int = 0, stream: int = 0):
         """Batched decode, pointer-array form (clay.h clay_decode_device_batch): chunks /
         out_chunks hold n_stripes * n entries, stripe s at [s * n, s * n + n), None where absent
-        as for decode_device; the None pattern must be the same in every stripe."""
+        as for decode_device; the None pattern must be the same in every stripe.  Pointer arrays
+        whose present inputs sit at one stripe stride and whose wanted outputs sit at one (rows of one
+        buffer) are eligible for the streaming batch exactly as decode_device_strided says; stripes
+        allocated separately run as before."""
         cnt = max(1, self.n * int(n_stripes))
         cp = (C.c_void_p * cnt)(*[(_ptr(x) if x is not None else None) for x in chunks])
         op = (C.c_void_p * cnt)(*[(_ptr(x) if x is not None else None) for x in out_chunks])

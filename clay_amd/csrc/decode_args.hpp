@@ -52,6 +52,13 @@ struct DecArgs {
     // k_stream_fused2: byte li = loader wave li's share of the rounds (decode_pattern.hpp f2_plan): bits
     // 0-1 its section, 2-3 its part, 4-5 the section's wave count - 1, bit 6 set (0: no rounds)
     uint32_t lwave;
+    // k_stream_local256 BATCH (decode_local256_batch.hip) only; every other kernel leaves them
+    // unread: nstripes stripes in one launch, stripe s's nodes at node[i] + s * sin and its outputs
+    // at out[r] + s * sout (node / out: stripe 0's), region / nslots the cut of ONE stripe and
+    // groups the groups of nslots workgroups per XCD (BatchMapOf<StreamMap>, stream_tile_map.hpp):
+    // grid = 8 * groups * nslots
+    int64_t sin, sout;
+    uint32_t nstripes, groups;
 };
 // k_stream_fused2: solver work items per lane and round (passes of 64 lanes over targets x 8
 // pieces, per iscore level) of the TWO instantiation (two erasures in a section) and of the other;

@@ -2281,14 +2281,34 @@ hipError_t launch_stream_local256_any_kernel(int kd, int g, const bs::DecArgs &a
                                              int dev);  // decode_local256_any.hip
 hipError_t launch_stream_fused2_kernel(int kd, const bs::DecArgs &a, hipStream_t stream, int dev,
                                        bool two);  // decode_stream.hip
+hipError_t launch_stream_local256_batch_kernel(int kd, int g, const bs::DecArgs &a, hipStream_t stream,
+                                               int dev);  // decode_local256_batch.hip
+
+// The launch geometry of k_stream_local256 BATCH: *groups = the G groups of nslots workgroups per
+// XCD that run one stripe's cut (stream_cut) side by side.  false: the kernel cannot take the batch
+// (fewer than 2 stripes, more than its 32-bit stripe index holds, or more loads for one workgroup
+// than its 32-bit load counter: 4 groups of at most 16 loads per tile)
+static bool local256_batch_geometry(const DevProps &prop, size_t ns, size_t sc, uint32_t *groups) {
+    if (ns < 2 || ns > 0xFFFFFFFFull) return false;
+    const bs::StreamCut cut = bs::stream_cut(sc, prop.per_xcd());
+    *groups = bs::batch_groups(prop.per_xcd(), cut.nslots, uint32_t(ns));
+    // StreamMap: at most region / (nslots * 256) full tiles and one partial per workgroup and stripe
+    const uint64_t tiles = uint64_t(cut.region) / (uint64_t(cut.nslots) * 256u) + 1u;
+    return tiles * ((ns + *groups - 1) / *groups) * 64u <= 0x7FFFFFFFull;
+}
 
 // One launch of the kernel `ch` names (bs::choose_decode, not DecKernel::None), no workspace.
 // `cin` / `cout`: internal node pointers (inputs of present nodes, outputs of erased nodes, nullptr
 // if not wanted).  Tables: t = r * 4 + j: row e_r of H_K^-1, check j; 16 + i * 4 + r: A_i[e_r] =
 // (H_K^-1 gamma H_i)[e_r]; kDecDetInv: (1 + gamma^2)^-1 for the kernels that invert both-erased pairs.
+// ns >= 2 (DecKernel::Local256 of (10,4,13) only, local256_batch_geometry holds): that pattern in
+// every one of ns stripes, stripe s = stripe 0's pointers + s * sin (inputs) / s * sout (outputs), in
+// ONE launch of the kernel's BATCH variant ("stream-local256-batch"); the tables go through
+// dec_tables once, nothing else is allocated.
 template <int KD>
 static Error launch_stream_decode(CodeState &cs, const DevProps &prop, const uint8_t *const *cin, uint8_t *const *cout,
-                                  const bs::DecChoice &ch, size_t sc, hipStream_t stream) {
+                                  const bs::DecChoice &ch, size_t sc, hipStream_t stream, size_t ns = 1, int64_t sin = 0,
+                                  int64_t sout = 0) {
     using S = bs::Shape<KD, 4>;
     static_assert(S::K == bs::kDecK && S::ALPHA == 256, "the codes decode_pattern.hpp is written for");
     if (Error e = rs_matches<S, 4>(cs)) return e;
@@ -2326,6 +2346,18 @@ static Error launch_stream_decode(CodeState &cs, const DevProps &prop, const uin
     } else {
         a.region = uint32_t(((sc + 7) / 8 + 63) / 64 * 64);
         a.nslots = std::min(prop.per_xcd(), std::max(1u, a.region / 64u));
+    }
+    if (ns >= 2) {
+        if (KD != 10 || ch.kernel != bs::DecKernel::Local256 || !local256_batch_geometry(prop, ns, sc, &a.groups))
+            return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "streaming decode batch: no kernel for this call");
+        a.nstripes = uint32_t(ns);
+        a.sin = sin;
+        a.sout = sout;
+        if (Error e = dec_tables(cs, prop, tabs, stream, &a.tabs)) return e;
+        CLAY_HIP(launch_stream_local256_batch_kernel(KD, ch.G, a, stream, prop.dev));
+        t_last_launches += 1;
+        t_last_exec = "stream-local256-batch";
+        return Error{};
     }
     if (Error e = dec_tables(cs, prop, tabs, stream, &a.tabs)) return e;
     switch (ch.kernel) {
@@ -2537,6 +2569,18 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
     return run_plan(cs, *plan, dev, *ds, static_cast<hipStream_t>(stream), P, chunk / c.sub_chunk_no, chunk);
 }
 
+// Auto's upper gate for the streaming decode batch ("stream-local256-batch"): the largest sub-chunk
+// of the sweep up to which the batch was no slower than the per-stripe loop in every swept cell --
+// sub-chunks 1,640 to 419,432, 2 / 4 / 16 / 64 stripes (cells up to 4 GiB of data), erasures {0} and
+// {0,4}; no slower: the batch's median at most the loop's plus the spread (max - min) of the loop's
+// samples (scripts/bench_paths.py ONLY=batch_decode_stream_gate, DESIGN.md 4.11,
+// profiles/r14/batch_decode_stream_gate.txt).  Up to 26,216 bytes the batch wins by 1.6x to 25x;
+// from 66,176, where one stripe fills the chip, by 2-6 %; at 262,152 {0} it ties (2 stripes 473 vs
+// 475 us, 4 stripes 936 vs 930 us, spread 4-8 us) and {0,4} wins by 2-3 %; at 419,432 it loses
+// (2 stripes {0} 699 vs 670 us), so auto keeps the loop there.
+// clay_amd.DECODE_STREAM_BATCH_AUTO_MAX_SC restates it (tests/test_local256_batch_gate_cpu.py).
+constexpr size_t kDecodeStreamBatchMaxSc = 262152;
+
 // ---- batched decode: n_stripes stripes with the same erasure set (clay_decode_device_strided /
 // clay_decode_device_batch) ----
 // in / out: the n chunks and the n output buffers of every stripe, both in the same form.  Pointer
@@ -2590,6 +2634,47 @@ static Error decode_batch_impl(const clay_code_t *code, StripeOperands in, const
     CodeState &cs = *o.cs;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int xmode = g_exec_mode.load(std::memory_order_relaxed);
+    // streaming batch: (10,4,13), 2 or more stripes whose pattern runs on k_stream_local256 on
+    // 8-byte rows (one erasure, or two in the shapes local_shape takes, 512 <= sc < 2^24), every
+    // present input at one stripe stride and every wanted output at one, both multiples of 8:
+    // ONE launch of the kernel's BATCH variant for any number of stripes.  "stream": every such
+    // call, the stripes of 4 MiB or less included; auto: only where the call would run stripe by
+    // stripe below, by the gate kDecodeStreamBatchMaxSc; no other mode ("stream-local" keeps one
+    // launch per stripe: the A/B partner).
+    if (n_stripes >= 2 && tn == 16 && c.k == 10 && c.m == 4 && c.q == 4 && c.t == 4 && chunk % c.sub_chunk_no == 0 &&
+        (xmode == kExecStream || (xmode == kExecAuto && c.k * chunk > kBatchMaxStripeBytes &&
+                                  chunk / c.sub_chunk_no <= kDecodeStreamBatchMaxSc))) {
+        const uint8_t *cin[16] = {};
+        uint8_t *cout[16] = {};
+        uint32_t gone_m = 0, alive_m = 0;
+        std::vector<size_t> present, wanted;
+        for (size_t i = 0; i < c.n; i++) {
+            const size_t b = internal_of(c, i);
+            if (erased[b]) {
+                cout[b] = want[b] ? o0[i] : nullptr;
+                if (cout[b]) wanted.push_back(i);
+            } else {
+                cin[b] = c0[i];
+                if (cin[b]) present.push_back(i);
+            }
+        }
+        for (size_t b = 0; b < 16; b++) {
+            gone_m |= erased[b] ? 1u << b : 0u;
+            alive_m |= cin[b] ? 1u << b : 0u;
+        }
+        const size_t sc = chunk / c.sub_chunk_no;
+        int64_t sin = 0, sout = 0;
+        uint32_t groups = 0;
+        if (!wanted.empty() && uniform_stride(in, 0, n_stripes, present.data(), present.size(), &sin) &&
+            uniform_stride(out, 0, n_stripes, wanted.data(), wanted.size(), &sout) && sin % 8 == 0 && sout % 8 == 0 &&
+            local256_batch_geometry(dev_props(dev), n_stripes, sc, &groups)) {
+            const bs::DecChoice ch =
+                bs::choose_decode(10, gone_m, alive_m, xmode, sc, !misaligned8(cin, 16) && !misaligned8(cout, 16),
+                                  tuning().decode_ring, tuning().local_w64);
+            if (ch.kernel == bs::DecKernel::Local256)
+                return launch_stream_decode<10>(cs, dev_props(dev), cin, cout, ch, sc, st, n_stripes, sin, sout);
+        }
+    }
     if (c.k * chunk <= kBatchMaxStripeBytes) {
         size_t n_erased = 0;
         for (size_t b = 0; b < tn; b++) n_erased += erased[b] && !is_shortened(c, b) ? 1 : 0;

@@ -83,38 +83,8 @@ __device__ __forceinline__ void ld16s2_masked(u32x4 &lo, u32x4 &hi, const uint8_
         : "v"(voff_lo), "v"(voff_hi), "s"(sbase), "s"(mask));
 }
 
-// (k_stream_encode's own tile map is BalancedMap, stream_tile_map.hpp; StreamMap serves the other
-// streaming kernels and the probe's old-map builds, PROBE 2097152)
-// XCD x owns bytes [x * region, min((x + 1) * region, sc)); full W-byte tiles round robin over
-// the XCD's ns workgroups, the remainder one partial tile per workgroup (its last), so every
-// workgroup of an XCD streams the same number of bytes to within 32.
-struct StreamMap {
-    uint32_t x0, x1, nfull, p0, p1, w;
-    __device__ StreamMap(uint32_t sc, uint32_t region, uint32_t ns, uint32_t xcd, uint32_t slot, uint32_t W = 256u) {
-        w = W;
-        x0 = xcd * region;
-        x1 = x0 + region < sc ? x0 + region : sc;
-        nfull = p0 = p1 = 0;
-        if (x0 >= x1) return;
-        const uint32_t len = x1 - x0, round = ns * W;
-        nfull = len / round;
-        const uint32_t left = len - nfull * round;
-        const uint32_t wp = ((left + ns - 1) / ns + 31u) & ~31u;
-        const uint32_t q0 = x0 + nfull * round + slot * wp;
-        if (left && q0 < x1) {
-            p0 = q0;
-            p1 = q0 + wp < x1 ? q0 + wp : x1;
-        }
-    }
-    __device__ int ntile() const { return int(nfull) + (p0 < p1 ? 1 : 0); }
-    __device__ StreamTile tile(int k, uint32_t slot, uint32_t ns) const {
-        if (uint32_t(k) < nfull) {
-            const uint32_t b0 = x0 + (uint32_t(k) * ns + slot) * w;
-            return {b0, b0 + w};
-        }
-        return {p0, p1};
-    }
-};
+// (k_stream_encode's own tile map is BalancedMap; StreamMap, which serves the other streaming
+// kernels and the probe's old-map builds, PROBE 2097152, is in stream_tile_map.hpp too)
 
 // Chip round robin (probe): full tile t -> workgroup t % G (the whole chip covers G adjacent
 // tiles at a time), the partial last tile to workgroup nfull % G.

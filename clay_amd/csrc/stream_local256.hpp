@@ -33,6 +33,8 @@
 // the 16-byte stores take any alignment, the partial pieces are patched and stored byte by byte).
 #pragma once
 
+#include <type_traits>
+
 #include "stream_decode.hpp"
 
 namespace clay {
@@ -42,10 +44,33 @@ namespace bs {
 // are shifted into place in LDS and stored byte by byte; the ANY = false instantiation keeps the
 // 8-byte tail handling (a separate kernel: the byte paths, though cold, slowed the 8-byte-row
 // kernel by 28 % when compiled into it)
-template <int KD, int G, int NE, bool ANY = false>
+// BATCH: many stripes in one launch (decode_local256_batch.hip): a tile carries its stripe
+// (StreamTile::stripe, BatchMapOf<StreamMap>) and the nodes / outputs of stripe s are a.node[i] +
+// s * a.sin and a.out[r] + s * a.sout.  The stripe is wave-uniform, so its offset goes into the
+// 64-bit uniform base of every access (stripe_off); the lanes' 32-bit offsets stay offsets in one
+// chunk.  The loader's flat load counter, the counted waits and the barriers run over the
+// workgroup's concatenated tile sequence unchanged.
+template <int KD, int G, int NE, bool ANY = false, bool BATCH = false>
 struct Local256 {
     using D = StreamDec<KD, G>;
     static_assert(NE == 1 || NE == 2, "one or two erased rows");
+    static_assert(!(BATCH && ANY), "the batch variant: 8-byte rows only");
+    // the workgroup's tile sequence: one stripe's cut, or that cut for each of its group's stripes
+    using Map = std::conditional_t<BATCH, BatchMapOf<StreamMap>, StreamMap>;
+    __device__ __forceinline__ static Map tile_map(const DecArgs &a, uint32_t xcd, uint32_t slot) {
+        if constexpr (BATCH) return Map(uint32_t(a.sc), a.region, a.nslots, a.groups, a.nstripes, xcd, slot);
+        else return Map(uint32_t(a.sc), a.region, a.nslots, xcd, slot);
+    }
+    // the compute waves' walk over the tile sequence (BATCH; else nothing)
+    struct NoWalk {
+        __device__ explicit NoWalk(const Map &) {}
+    };
+    using Walk = std::conditional_t<BATCH, typename BatchMapOf<StreamMap>::Walk, NoWalk>;
+    // byte offset of tile t's stripe in a node family of stripe stride `stride` (BATCH; else 0)
+    __device__ __forceinline__ static int64_t stripe_off(StreamTile t, int64_t stride) {
+        if constexpr (BATCH) return int64_t(t.stripe) * stride;
+        else return 0;
+    }
     static constexpr int W = 256, CWAVES = 8, LOADERS = 4, BLOCK = 64 * (CWAVES + LOADERS);
     static constexpr int BUF = 16384;  // 64 columns x 256 B
     static constexpr int BPL = 16 / LOADERS;
@@ -85,6 +110,7 @@ struct Local256 {
                                  uint32_t b) {
         const uint32_t sc = uint32_t(a.sc);
         lds_buf = __builtin_amdgcn_readfirstlane(lds_buf) + uint32_t(L.li * BPL) * 1024u;
+        if constexpr (BATCH) node += stripe_off(t, a.sin);
         const uint64_t gofs = uint64_t(b * D::wt(G)) * sc;
         if (t.vend >= t.b0 + uint32_t(W)) {
             const uint8_t *base = uniform_ptr(node + gofs + t.b0);
@@ -108,6 +134,7 @@ struct Local256 {
                                  uint32_t b, int lane) {
         const uint32_t sc = uint32_t(a.sc), pos = t.b0 + L.k16;
         if (!(pos < t.vend && pos + 16u > t.vend)) return;
+        if constexpr (BATCH) node += stripe_off(t, a.sin);
         if constexpr (!ANY) {
 #pragma unroll
             for (int j = 0; j < BPL; j++) {
@@ -320,17 +347,20 @@ struct Local256 {
     }
 };
 
-// grid = 8 * nslots (one workgroup per CU); LDS = 10 x 16 KiB: a ring of a.ring - 1 node
+// grid = 8 * nslots (one workgroup per CU; BATCH: per group); LDS = 10 x 16 KiB: a ring of a.ring - 1 node
 // buffers and the tables (presolve, A_i) in the last.  a.region: XCD region bytes (multiple of 32).
-template <int KD, int G, int NE, bool ANY = false>
-__global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_local256(DecArgs a) {
-    using Kn = Local256<KD, G, NE, ANY>;
+// BATCH: grid = 8 * a.groups * a.nslots; workgroup slot = blockIdx.x / 8 is sub-slot slot % nslots of
+// group slot / nslots, which runs the stripes of its group back to back (a group without a stripe
+// has no tile and leaves with the workgroups of empty XCD regions)
+template <int KD, int G, int NE, bool ANY = false, bool BATCH = false>
+__global__ __launch_bounds__((Local256<KD, G, NE, ANY, BATCH>::BLOCK)) void k_stream_local256(DecArgs a) {
+    using Kn = Local256<KD, G, NE, ANY, BATCH>;
     using D = typename Kn::D;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint32_t xcd = blockIdx.x & 7u, wslot = blockIdx.x >> 3, ns = a.nslots;
     const uint32_t sc = uint32_t(a.sc);
-    const StreamMap tm(sc, a.region, ns, xcd, wslot);
+    const typename Kn::Map tm = Kn::tile_map(a, xcd, wslot);
     const uint32_t ntile = uint32_t(tm.ntile());
     if (ntile == 0) return;  // uniform per workgroup
     const uint32_t R = a.ring - 1u, NT = a.nt;
@@ -383,8 +413,12 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
     const uint32_t c0 = uint32_t(threadIdx.x) >> 3, p0 = uint32_t(threadIdx.x) & 7u;
     const uint32_t eG = a.emask[G];
     const bool has2 = a.g2 >= 0;
+    [[maybe_unused]] typename Kn::Walk walk(tm);
     for (uint32_t k = 0; k < ntile; k++) {
-        const StreamTile t = tm.tile(int(k), wslot, ns);
+        // the tile is needed for the outputs only; BATCH: taken there, from the map's walk (no
+        // division where the rows C are live)
+        StreamTile t;
+        if constexpr (!BATCH) t = tm.tile(int(k), wslot, ns);
         uint32_t C[NE][4][8];
 #pragma unroll
         for (int r = 0; r < NE; r++)
@@ -439,11 +473,15 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
         }
         const uint8_t *tl = smem + R * BUF + opq(0u);
         const uint32_t c = opq(c0), p = opq(p0);
+        // the solve's copy of eG; BATCH: opaque per tile, so that its bit tests are made here and not
+        // held as loop-invariant lane masks across the tile (registers the walk's state needs)
+        uint32_t eGs = eG;
+        if constexpr (BATCH) asm volatile("" : "+s"(eGs));
         // (i) g2-lines of the groups outside E_G (sources: level-0 values)
         if (has2) {
             sfor<4>([&](auto gc) BS_INL {
                 constexpr int g = decltype(gc)::value;
-                if (!((eG >> g) & 1u)) Kn::line_g2(a, C, tl, c, g);
+                if (!((eGs >> g) & 1u)) Kn::line_g2(a, C, tl, c, g);
             });
         }
         // (ii) groups g in E_G: the in-lane terms of the used nodes (G, A), A not in E_G
@@ -451,11 +489,11 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
             const uint32_t used_all = a.used;
             sfor<4>([&](auto gc) BS_INL {
                 constexpr int g = decltype(gc)::value;
-                if (!((eG >> g) & 1u)) return;
+                if (!((eGs >> g) & 1u)) return;
                 const uint32_t rg = uint32_t(a.rix[4 * G + g]);
                 sfor<4>([&](auto ac) BS_INL {
                     constexpr int A = decltype(ac)::value;
-                    if (((eG >> A) & 1u) || !((used_all >> (4 * G + A)) & 1u)) return;
+                    if (((eGs >> A) & 1u) || !((used_all >> (4 * G + A)) & 1u)) return;
                     uint32_t v[8];
                     Kn::get(C, rg, A, v);
                     Kn::add_mul(C, tl, 16 + (4 * G + A) * 4, v, g);
@@ -466,14 +504,14 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
         if (has2) {
             sfor<4>([&](auto gc) BS_INL {
                 constexpr int g = decltype(gc)::value;
-                if ((eG >> g) & 1u) Kn::line_g2(a, C, tl, c, g);
+                if ((eGs >> g) & 1u) Kn::line_g2(a, C, tl, c, g);
             });
         }
         // (iv) a both-erased pair of section G (two erasures there, none elsewhere): (G, x) at
         // group g <-> (G, g) at group x, C = det^-1 (U + gamma U*) (transforms.rs:108-125)
         if constexpr (NE == 2) {
-            if (__builtin_popcount(eG) == 2) {
-                const uint32_t gl = uint32_t(__builtin_ctz(eG)), xh = 31u - uint32_t(__builtin_clz(eG));
+            if (__builtin_popcount(eGs) == 2) {
+                const uint32_t gl = uint32_t(__builtin_ctz(eGs)), xh = 31u - uint32_t(__builtin_clz(eGs));
                 const uint32_t rx = uint32_t(a.rix[4 * G + xh]), rg = uint32_t(a.rix[4 * G + gl]);
                 const GfTab dinv = D::tab_at(tl, kDecDetInv);
                 sfor<4>([&](auto gc) BS_INL {
@@ -497,6 +535,11 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
             }
         }
         // outputs: pieces p and 8 + p of row (layer z) per erased row and group
+        [[maybe_unused]] int64_t ooff = 0;  // the stripe's offset in every output
+        if constexpr (BATCH) {
+            t = walk.next(tm);
+            ooff = Kn::stripe_off(t, a.sout);
+        }
         const bool full = t.vend >= t.b0 + uint32_t(Kn::W);
         if (full) {
             // lanes c and c ^ 1 (lane ^ 8) swap halves by DPP (as the encode's parity stores), so
@@ -508,6 +551,7 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
             for (int r = 0; r < NE; r++) {
                 const uint8_t *base = uniform_ptr(a.out[r]);
                 if (!base) continue;
+                if constexpr (BATCH) base = uniform_ptr(base + ooff);
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
                     uint32_t lo[4], hi[4];
@@ -529,6 +573,7 @@ __global__ __launch_bounds__((Local256<KD, G, NE, ANY>::BLOCK)) void k_stream_lo
             for (int r = 0; r < NE; r++) {
                 uint8_t *dst = a.out[r];
                 if (!dst) continue;
+                if constexpr (BATCH) dst += ooff;
 #pragma unroll
                 for (int g = 0; g < 4; g++) {
                     uint8_t *row = dst + uint64_t(z0 + uint32_t(g) * D::wt(G)) * sc + t.b0 + 16u * p;

@@ -1,7 +1,10 @@
-// stream_tile_map.hpp -- how k_stream_encode cuts a sub-chunk row of sc bytes into tiles.
-// Plain integer code (no HIP builtins), so that a host program can include it and walk the map
-// (tests/test_stream_tile_map_cpu.py).
+// stream_tile_map.hpp -- how the streaming kernels cut a sub-chunk row of sc bytes into tiles:
+// BalancedMap (k_stream_encode), StreamMap (k_stream_local256 and the other streaming kernels) and
+// the batch grouping over either (BatchMapOf).
+// Plain integer code (no HIP builtins), so that a host program can include it and walk the maps
+// (tests/test_stream_tile_map_cpu.py, tests/test_local256_batch_map_cpu.py).
 //
+// BalancedMap.
 // XCD x owns bytes [x * region, min((x + 1) * region, sc)) of every row (region: a multiple of
 // 32); its ns workgroups (slots) cover that region in R = ceil(len / (ns * 256)) rounds, the
 // fewest a 256-byte tile allows.  Instead of R - 1 rounds of full tiles and a narrow last one
@@ -64,9 +67,43 @@ struct BalancedMap {
     }
 };
 
-// A batch of n_stripes stripes of one sub-chunk size in one launch (k_stream_encode BATCH).
+// StreamMap (k_stream_local256, the repair and 3-parity encode kernels, the encode probe's old-map
+// builds): XCD x owns bytes [x * region, min((x + 1) * region, sc)); full W-byte tiles round robin
+// over the XCD's ns workgroups, the remainder one partial tile per workgroup (its last), so every
+// workgroup of an XCD streams the same number of bytes to within 32.
+struct StreamMap {
+    uint32_t x0, x1, nfull, p0, p1, w;
+    CLAY_TILE_MAP_HD StreamMap(uint32_t sc, uint32_t region, uint32_t ns, uint32_t xcd, uint32_t slot, uint32_t W = 256u) {
+        w = W;
+        x0 = xcd * region;
+        x1 = x0 + region < sc ? x0 + region : sc;
+        nfull = p0 = p1 = 0;
+        if (x0 >= x1) return;
+        const uint32_t len = x1 - x0, round = ns * W;
+        nfull = len / round;
+        const uint32_t left = len - nfull * round;
+        const uint32_t wp = ((left + ns - 1) / ns + 31u) & ~31u;
+        const uint32_t q0 = x0 + nfull * round + slot * wp;
+        if (left && q0 < x1) {
+            p0 = q0;
+            p1 = q0 + wp < x1 ? q0 + wp : x1;
+        }
+    }
+    CLAY_TILE_MAP_HD int ntile() const { return int(nfull) + (p0 < p1 ? 1 : 0); }
+    CLAY_TILE_MAP_HD StreamTile tile(int k, uint32_t slot, uint32_t ns) const {
+        if (uint32_t(k) < nfull) {
+            const uint32_t b0 = x0 + (uint32_t(k) * ns + slot) * w;
+            return {b0, b0 + w, 0u};
+        }
+        return {p0, p1, 0u};
+    }
+};
+
+// A batch of n_stripes stripes of one sub-chunk size in one launch (k_stream_encode BATCH with
+// One = BalancedMap, k_stream_local256 BATCH with One = StreamMap: BatchMapOf<One>).
 // Every stripe keeps exactly the one-stripe cut: its region, ns = nsS workgroups per XCD and
-// BalancedMap(sc, region, nsS, xcd, sub).  The per_xcd workgroups of an XCD form
+// One(sc, region, nsS, xcd, sub); the encode's words below (BalancedMap, rounds) read the same for
+// StreamMap and its tiles.  The per_xcd workgroups of an XCD form
 // G = min(max(1, per_xcd / nsS), n_stripes) groups of nsS (batch_groups); workgroup `slot` is
 // sub-slot slot % nsS of group j = slot / nsS, and slots from G * nsS on are not launched (grid =
 // 8 * G * nsS).  Group j runs the stripes j, j + G, j + 2G, ... one after the other, each through
@@ -94,27 +131,47 @@ CLAY_TILE_MAP_HD inline StreamCut stream_cut(uint64_t sc, uint32_t per_xcd, uint
     return {region, per_xcd < tiles ? per_xcd : tiles};
 }
 
-struct BatchMap {
-    BalancedMap one;  // the cut of every stripe, for this workgroup's sub-slot
-    uint32_t ns, sub, first, groups, count;
-    CLAY_TILE_MAP_HD BatchMap(uint32_t sc, uint32_t region, uint32_t ns_, uint32_t groups_, uint32_t n_stripes, uint32_t xcd,
-                              uint32_t slot)
+template <class One>
+struct BatchMapOf {
+    One one;  // the cut of every stripe, for this workgroup's sub-slot
+    uint32_t ns, sub, first, groups, count, nt;  // nt: one.ntile(), the tiles of one stripe
+    CLAY_TILE_MAP_HD BatchMapOf(uint32_t sc, uint32_t region, uint32_t ns_, uint32_t groups_, uint32_t n_stripes, uint32_t xcd,
+                                uint32_t slot)
         : one(sc, region, ns_, xcd, slot % ns_), ns(ns_), sub(slot % ns_), first(slot / ns_), groups(groups_) {
         // stripes first, first + G, ... below n_stripes; none for a slot at or past G * ns
         count = first < groups && first < n_stripes ? (n_stripes - first + groups - 1u) / groups : 0u;
+        nt = uint32_t(one.ntile());
     }
     CLAY_TILE_MAP_HD int stripes() const { return int(count); }
-    CLAY_TILE_MAP_HD int ntile() const { return one.ntile() * int(count); }
+    CLAY_TILE_MAP_HD int ntile() const { return int(nt * count); }
     // stripe of the workgroup's tile k
-    CLAY_TILE_MAP_HD uint32_t stripe(int k) const { return first + uint32_t(k) / one.nt * groups; }
+    CLAY_TILE_MAP_HD uint32_t stripe(int k) const { return first + uint32_t(k) / nt * groups; }
     // (slot and ns of the one-stripe maps' signature are not used: the map holds its own)
     CLAY_TILE_MAP_HD StreamTile tile(int k, uint32_t, uint32_t) const {
-        const uint32_t i = uint32_t(k) / one.nt;
-        StreamTile t = one.tile(int(uint32_t(k) - i * one.nt), sub, ns);
+        const uint32_t i = uint32_t(k) / nt;
+        StreamTile t = one.tile(int(uint32_t(k) - i * nt), sub, ns);
         t.stripe = first + i * groups;
         return t;
     }
+    // The same sequence, tile after tile, without the division by nt: next() returns tile(k) for
+    // k = 0, 1, 2, ... (k_stream_local256's compute waves, which have no registers to spare for the
+    // division's temporaries where they need the tile; tests/host/local256_batch_map_check.cpp
+    // walks both and compares).  Not to be called more than ntile() times.
+    struct Walk {
+        uint32_t r, stripe;
+        CLAY_TILE_MAP_HD explicit Walk(const BatchMapOf &m) : r(0u), stripe(m.first) {}
+        CLAY_TILE_MAP_HD StreamTile next(const BatchMapOf &m) {
+            StreamTile t = m.one.tile(int(r), m.sub, m.ns);
+            t.stripe = stripe;
+            if (++r == m.nt) {
+                r = 0u;
+                stripe += m.groups;
+            }
+            return t;
+        }
+    };
 };
+using BatchMap = BatchMapOf<BalancedMap>;  // k_stream_encode BATCH
 
 }  // namespace bs
 }  // namespace clay

@@ -313,7 +313,31 @@ int clay_decode_device_codeword(const clay_code_t *code, const uint8_t *const *c
  * unprepared), anything else, from 4 stripes, as one k_gexec launch per level of the decode plan
  * ("grouped-batch"; inside a stream capture it must have been prepared by one call of the same
  * shape, like clay_decode_device); fewer or larger stripes run stripe by stripe as
- * clay_decode_device.  Asynchronous on `stream`. */
+ * clay_decode_device.
+ * The streaming batch: (10,4,13) stripes whose pattern runs on the local decode on 256-byte row
+ * runs can run as ONE launch of that kernel's batch variant for any number of stripes (last exec
+ * path "stream-local256-batch", clay_last_launch_count() 1).  A call is eligible when
+ *   - the code is (10,4,13) and n_stripes >= 2;
+ *   - stripe 0's pattern is one the one-stripe call runs on k_stream_local256 on 8-byte rows: every
+ *     1-erasure and every 2-erasure pattern, a sub-chunk that is a multiple of 8 with
+ *     512 <= sub-chunk < 2^24, every chunk 8-byte aligned;
+ *   - every present node's input sits at one stripe stride and every rebuilt output at one (the
+ *     strided form by construction; pointer arrays that are rows of one buffer);
+ *   - both stripe strides are multiples of 8, so every stripe is on 8-byte rows.
+ * The overlap rule above applies unchanged; out == chunks in place is allowed (erased slots are
+ * never read).  Which exec modes take it:
+ *   "stream"         every eligible call at any eligible size, stripes of <= 4 MiB included
+ *   auto             only calls that would run stripe by stripe (more than 4 MiB of data per
+ *                    stripe), for sub-chunks up to the measured gate kDecodeStreamBatchMaxSc =
+ *                    262,152 bytes: above it (the 1 GiB stripe's 419,432) the batch lost to the
+ *                    loop and auto keeps one launch per stripe
+ *   "stream-local"   never: one launch per stripe ("stream-local256"), the A/B partner
+ *   "grouped", "tile"  never
+ *   "stream-fused2"  unchanged
+ * The pattern's table is uploaded once per pattern: inside a stream capture the call needs one warm
+ * call of the same pattern first (else the "not prepared" error, nothing launched); nothing else is
+ * allocated.  (9,4,12), rows off 8-byte alignment and 3-4 erasures keep the paths above.
+ * Asynchronous on `stream`. */
 int clay_decode_device_strided(const clay_code_t *code, const uint8_t *chunks, int64_t node_stride,
                                int64_t stripe_stride, const size_t *erasures, size_t n_erasures,
                                uint8_t *out, int64_t out_node_stride, int64_t out_stripe_stride,
@@ -468,7 +492,9 @@ int clay_set_encode_path(int mode);
  *                data): (4,2,5) with one erasure at uniform stripe strides in one launch of
  *                the batched k_bs_decode1 ("bs-decode1-batch"), every other code, pattern or
  *                layout, from 4 stripes, one k_gexec launch per plan level for the whole batch
- *                ("grouped-batch"); batched repairs (clay_repair_device_strided / _batch, same
+ *                ("grouped-batch"; larger (10,4,13) stripes with one or two erasures: the streaming
+ *                batch, "stream-local256-batch", up to the gate of clay_decode_device_strided);
+ *                batched repairs (clay_repair_device_strided / _batch, same
  *                stripe sizes): q = m codes with a k_bs_repair instantiation from all n - 1 other
  *                nodes at uniform stripe strides in one launch of the batched k_bs_repair
  *                ("bs-repair-batch"), every other code, helper set or layout, from 4 stripes,
@@ -490,10 +516,13 @@ int clay_set_encode_path(int mode);
  *    under 1 / 2, and under 3 stream only with scrub path 1; everything else on v1 in every mode)
  *   3 stream  -- every decode a streaming kernel takes on it: the local decode where it takes
  *                the pattern (the (2,1) patterns: the fused decode v2 first), else the fused
- *                decode v2 (2-4 erasures, at most two per section); everything else as auto
+ *                decode v2 (2-4 erasures, at most two per section); batched decodes of (10,4,13)
+ *                eligible for the streaming batch (clay_decode_device_strided) in one launch,
+ *                "stream-local256-batch", at any eligible size; everything else as auto
  *   5 stream-local -- every decode a local kernel takes on it ("stream-local256" /
  *                "stream-local", the (2,1) patterns included); every other decode on auto's
- *                plan executors (no fused decode v2, no k_bs_decode1)
+ *                plan executors (no fused decode v2, no k_bs_decode1); never the streaming batch
+ *                (one launch per stripe: its A/B partner)
  *   6 stream-fused2 -- decodes of 2-4 erasures with at most two per y-section on the fused
  *                decode v2 (k_stream_fused2, "stream-fused2"; ring of 10 - e node buffers: a
  *                section's surviving real nodes fit it, two neighbouring sections that do not

@@ -10,6 +10,9 @@ ONLY=batch_stream: many (10,4,13) stripes above 4 MiB per call, the streaming ba
 per-stripe loop; batch_stream_gate: the sweep behind auto's upper gate for it.
 ONLY=scrub_batch_stream: many (10,4,13) stripes scrubbed in one launch of the streaming batch, the
 path without it and the batched encode alternated; scrub_batch_gate: the sweep behind auto's gate.
+ONLY=batch_decode_stream: many (10,4,13) stripes with the same lost nodes decoded in one launch of
+the local decode's batch variant against the per-stripe loop; batch_decode_stream_gate: the sweep
+behind auto's gate for it.
 Prints one JSON object per configuration."""
 import json
 import os
@@ -476,6 +479,76 @@ def batch_stream_cfg(sc, n, k=10, m=4, d=13, gate=False):
     print(json.dumps(out), flush=True)
 
 
+def batch_decode_stream_cfg(sc, n, er, gate=False, samples=None):
+    """ONLY=batch_decode_stream / batch_decode_stream_gate: n stripes of (10,4,13) at sub-chunk sc
+    with the nodes `er` lost in every stripe through clay_decode_device_strided, as ONE launch of the
+    local decode's batch variant (exec mode "stream", "stream-local256-batch") and as the library's
+    per-stripe loop (exec mode "stream-local", n launches of "stream-local256": the path without the
+    batch), samples alternated in one run, B2B back-to-back calls per sample.  Per leg: the samples,
+    median, min and spread (max - min) per call of n stripes, and GiB/s of stripe data.  gate: also
+    "batch_no_slower" -- the batch's median is at most the loop's plus the spread of the loop's
+    samples (the A/B's own run-to-run spread) -- and "batch_wins" -- below it by more than that."""
+    global RUNS
+    c = ClayCode(10, 4, 13)
+    k = 10
+    chunk = c.sub_chunk_no * sc
+    full = rnd(n * c.n, chunk, 31).view(n, c.n, chunk)
+    outs = torch.empty((n, c.n, chunk), dtype=torch.uint8, device="cuda")
+    er = list(er)
+
+    def call(mode):
+        def fn():
+            clay_amd.set_exec_mode(mode)
+            c.decode_device_strided(full, er, outs, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
+        return fn
+
+    legs = [("batch", call("stream")), ("loop", call("stream-local"))]
+    keep = RUNS
+    if samples:
+        RUNS = samples
+    try:
+        info, ref = {}, None
+        for tag, fn in legs:
+            outs.fill_(0)
+            fn()
+            torch.cuda.synchronize()
+            info[tag] = (clay_amd.last_exec_path(), clay_amd.last_launch_count())
+            if ref is None:
+                ref = outs[:, er].clone()
+            else:
+                assert torch.equal(outs[:, er], ref), "the two legs differ"
+        ts = {tag: [] for tag, _ in legs}
+        for i in range(RUNS + 2):
+            for tag, fn in legs:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                fn()
+                e0.record(stream)
+                for _ in range(B2B):
+                    fn()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                if i >= 2:
+                    ts[tag].append(e0.elapsed_time(e1) / B2B)
+        out = {"config": f"decode (10,4,13) batch_decode_stream {n} x {k * chunk / 2**20:.1f} MiB (sc {sc}) erasures {er}",
+               "stripe_data_bytes": n * k * chunk}
+        for tag, _ in legs:
+            t = ts[tag]
+            med = float(np.median(t))
+            out[tag] = {"path": info[tag][0], "launches": info[tag][1],
+                        "us": [round(x * 1e3, 2) for x in t], "median_us": round(med * 1e3, 2),
+                        "min_us": round(float(np.min(t)) * 1e3, 2),
+                        "spread_us": round(float(np.max(t) - np.min(t)) * 1e3, 2),
+                        "stripe_data_GiBps": round(n * k * chunk / (med * 1e-3) / 2**30, 1)}
+        if gate:
+            d = out["loop"]["median_us"] - out["batch"]["median_us"]
+            out["batch_no_slower"] = bool(d >= -out["loop"]["spread_us"])
+            out["batch_wins"] = bool(d > out["loop"]["spread_us"])
+        print(json.dumps(out), flush=True)
+    finally:
+        RUNS = keep
+        clay_amd.set_exec_mode(EXEC)
+
+
 def _scrub_partner(sc):
     """The exec mode under which scrub path 'auto' runs what a library without the streaming batch
     runs for a batch of (10,4,13) at sub-chunk sc under exec auto: from 65,536 the per-stripe
@@ -610,6 +683,19 @@ if __name__ == "__main__":
             # stripe already fills the chip (one group: only the launch seams are saved)
             *[("batch_stream_gate", (lambda sc=sc, n=n: batch_stream_cfg(sc, n, gate=True)))
               for sc in (32776, 66176, 131080, 262152, 419432) for n in (2, 3, 4, 6)],
+            # ONLY=batch_decode_stream: 1 GiB of (10,4,13) data as 64 stripes of 16 MiB, 205 of 5 MiB,
+            # 16 of 64 MiB and, for scale, one stripe of 1 GiB (a one-stripe call: the same path in
+            # both legs), node 0 and nodes 0 and 4 lost (DESIGN.md 4.11 "Streaming batches")
+            *[("batch_decode_stream", (lambda sc=sc, n=n, er=er: batch_decode_stream_cfg(sc, n, er)))
+              for er in ([0], [0, 4]) for sc, n in ((6560, 64), (2048, 205), (26216, 16), (419432, 1))],
+            # ONLY=batch_decode_stream_gate: the sweep behind auto's gate: sub-chunks from just above the
+            # staged batch's 4 MiB of data per stripe (sc 1,640) to the benchmark's 419,432, 2 / 4 / 16 /
+            # 64 stripes (cells of more than 4 GiB of stripe data are left out: they do not fit the
+            # run's time), both patterns, at least 5 samples per leg
+            *[("batch_decode_stream_gate", (lambda sc=sc, n=n, er=er: batch_decode_stream_cfg(
+                sc, n, er, gate=True, samples=max(5, RUNS // 2))))
+              for sc in (1640, 2048, 6560, 26216, 66176, 131080, 262152, 419432) for n in (2, 4, 16, 64)
+              if n * 2560 * sc <= 4 << 30 for er in ([0], [0, 4])],
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 1 << 10, 65536, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 10 << 10, 6553, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 100 << 10, 655, 0, 655)),
