@@ -28,7 +28,7 @@ __all__ = [
     "InsufficientHelperData", "InconsistentChunkSizes", "TooManyErasures",
     "ReconstructionFailed", "MissingYSectionHelper", "Overflow", "DeviceError",
     "set_encode_path", "last_encode_path", "last_launch_count", "set_exec_mode", "last_exec_path",
-    "set_scrub_path", "DECODE_STREAM_BATCH_AUTO_MAX_SC",
+    "set_scrub_path", "DECODE_STREAM_BATCH_AUTO_MAX_SC", "DECODE_FUSED2_BATCH_AUTO_MAX_SC",
 ]
 
 
@@ -124,6 +124,14 @@ _EXEC_MODES = {"auto": 0, "grouped": 1, "tile": 2, "stream": 3, "stream-local": 
 # (tests/test_local256_batch_gate_cpu.py compares the two).
 DECODE_STREAM_BATCH_AUTO_MAX_SC = 262152
 
+# The same gate for the batch of the fused decode v2 ('stream-fused2-batch': 3-4 erasures): the
+# largest swept sub-chunk up to which that batch was no slower than the per-stripe loop in every
+# cell of its sweep (profiles/r15/batch_decode_fused2_gate.txt: it won every cell, so this is the
+# sweep's largest sub-chunk); 0 would mean 'auto' never takes it.
+# Restates kDecodeFused2BatchMaxSc of csrc/engine.hip (tests/test_fused2_batch_gate_cpu.py compares
+# the two).
+DECODE_FUSED2_BATCH_AUTO_MAX_SC = 419432
+
 
 def set_exec_mode(mode: str) -> str:
     """Process-wide plan executor for decode / repair / staged encode (clay.h): 'auto' (tile-fused
@@ -140,7 +148,14 @@ def set_exec_mode(mode: str) -> str:
     eligible size; under 'auto' only for stripes of more than 4 MiB of data with sub-chunks up to
     DECODE_STREAM_BATCH_AUTO_MAX_SC = 262,152 bytes (the measured gate of clay.h);
     'stream-local' keeps one launch per stripe ('stream-local256', the A/B partner), 'grouped' /
-    'tile' never take it and 'stream-fused2' is unchanged.  Modes choose kernels
+    'tile' never take it and 'stream-fused2' is unchanged.  Batched decodes of (10,4,13) whose
+    pattern 'stream' runs on the fused decode v2 (352 of the 364 three-erasure and 878 of the 1,001
+    four-erasure patterns) are ONE launch of that kernel's batch variant ('stream-fused2-batch')
+    under 'stream' at any eligible size, and under 'auto' only for stripes of more than 4 MiB of data
+    with sub-chunks up to DECODE_FUSED2_BATCH_AUTO_MAX_SC = 419,432 bytes (the largest swept);
+    'stream-fused2' keeps one
+    launch per stripe (the A/B partner), 'stream-local', 'grouped' and 'tile' never take it.
+    Modes choose kernels
     only: every mode returns the reference's bytes on any input.  The scrub of (4,2,5) runs the
     line kernel ('bs-scrub1') except under 'grouped' / 'tile', which keep the v1 kernel
     ('bs-scrub') for A/B.  The scrub of (10,4,13) on 8-byte rows (sub-chunk a multiple of 8 and at
@@ -184,8 +199,9 @@ def set_scrub_path(name: str) -> str:
 def last_exec_path() -> str:
     """Plan executor of this thread's last decode / repair / staged encode: 'tile' | 'grouped' |
     'stream-local256' | 'stream-local' | 'stream-fused2' | 'bs-decode1' | 'bs-repair-stream' | 'bs-repair' |
-    'bs-decode1-batch' / 'stream-local256-batch' (the batched decodes in one launch: (4,2,5) on the line
-    kernel, (10,4,13) on the 256-byte-run local decode) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
+    'bs-decode1-batch' / 'stream-local256-batch' / 'stream-fused2-batch' (the batched decodes in one
+    launch: (4,2,5) on the line kernel, (10,4,13) on the 256-byte-run local decode and, with 3-4
+    erasures, on the fused decode v2) | 'bs-repair-batch' (the batched repairs) | 'grouped-batch'
     (both) | the scrubs' 'bs-scrub1' / 'bs-scrub' (one launch per stripe), 'bs-scrub1-batch' /
     'bs-scrub-batch' (a batch in one launch), 'stream-scrub' ((10,4,13) on the streaming kernel:
     one launch per stripe in every entry point) and 'stream-scrub-batch' (many stripes in one
@@ -513,7 +529,15 @@ class ClayCode:
         stripes of 4 MiB or less included ('grouped-batch' otherwise); 'auto' only stripes of more
         than 4 MiB of data with sub-chunks up to DECODE_STREAM_BATCH_AUTO_MAX_SC = 262,152 bytes;
         'stream-local' (one launch per stripe, the A/B partner), 'grouped' and 'tile' never;
-        'stream-fused2' is unchanged.  Anything not eligible runs as before.  Inside a stream
+        'stream-fused2' is unchanged.
+
+        Three and four erasures ('stream-fused2-batch', one launch as well): the same conditions with
+        a pattern exec mode 'stream' runs on the fused decode v2 (at most two erasures per
+        y-section: 352 of the 364 three-erasure and 878 of the 1,001 four-erasure patterns).
+        'stream' takes every such call; 'auto' only stripes of more than 4 MiB of data with
+        sub-chunks up to DECODE_FUSED2_BATCH_AUTO_MAX_SC = 419,432 bytes (below 4 MiB
+        'grouped-batch' stays); 'stream-fused2' keeps one launch per stripe (the A/B partner); 'stream-local',
+        'grouped' and 'tile' never.  Anything not eligible runs as before.  Inside a stream
         capture the call needs one warm call of the same pattern first (its table upload)."""
         ns_ = node_stride or chunk_size
         ss_ = stripe_stride or self.n * chunk_size
@@ -534,7 +558,8 @@ class ClayCode:
         out_chunks hold n_stripes * n entries, stripe s at [s * n, s * n + n), None where absent
         as for decode_device; the None pattern must be the same in every stripe.  Pointer arrays
         whose present inputs sit at one stripe stride and whose wanted outputs sit at one (rows of one
-        buffer) are eligible for the streaming batch exactly as decode_device_strided says; stripes
+        buffer) are eligible for the streaming batch ('stream-local256-batch', or
+        'stream-fused2-batch' with 3-4 erasures) exactly as decode_device_strided says; stripes
         allocated separately run as before."""
         cnt = max(1, self.n * int(n_stripes))
         cp = (C.c_void_p * cnt)(*[(_ptr(x) if x is not None else None) for x in chunks])

@@ -2283,6 +2283,8 @@ hipError_t launch_stream_fused2_kernel(int kd, const bs::DecArgs &a, hipStream_t
                                        bool two);  // decode_stream.hip
 hipError_t launch_stream_local256_batch_kernel(int kd, int g, const bs::DecArgs &a, hipStream_t stream,
                                                int dev);  // decode_local256_batch.hip
+hipError_t launch_stream_fused2_batch_kernel(int kd, const bs::DecArgs &a, hipStream_t stream, int dev,
+                                             bool two);  // decode_fused2_batch.hip
 
 // The launch geometry of k_stream_local256 BATCH: *groups = the G groups of nslots workgroups per
 // XCD that run one stripe's cut (stream_cut) side by side.  false: the kernel cannot take the batch
@@ -2297,14 +2299,28 @@ static bool local256_batch_geometry(const DevProps &prop, size_t ns, size_t sc, 
     return tiles * ((ns + *groups - 1) / *groups) * 64u <= 0x7FFFFFFFull;
 }
 
+// The launch geometry of k_stream_fused2 BATCH, in the same manner: the G groups of nslots
+// workgroups per XCD that run one stripe's 64-byte round-robin cut (round_robin_cut) side by side.
+// false: fewer than 2 stripes, more than the 32-bit stripe index holds, or more loads for one
+// workgroup than the kernel's 32-bit load counter (at most 16 loads per tile; a workgroup has at
+// most ceil(region / 64 / nslots) tiles per stripe)
+static bool fused2_batch_geometry(const DevProps &prop, size_t ns, size_t sc, uint32_t *groups) {
+    if (ns < 2 || ns > 0xFFFFFFFFull) return false;
+    const bs::StreamCut cut = bs::round_robin_cut(sc, prop.per_xcd());
+    *groups = bs::batch_groups(prop.per_xcd(), cut.nslots, uint32_t(ns));
+    const uint64_t tiles = (uint64_t(cut.region) / 64u + cut.nslots - 1u) / cut.nslots;
+    return tiles * ((ns + *groups - 1) / *groups) * 16u <= 0x7FFFFFFFull;
+}
+
 // One launch of the kernel `ch` names (bs::choose_decode, not DecKernel::None), no workspace.
 // `cin` / `cout`: internal node pointers (inputs of present nodes, outputs of erased nodes, nullptr
 // if not wanted).  Tables: t = r * 4 + j: row e_r of H_K^-1, check j; 16 + i * 4 + r: A_i[e_r] =
 // (H_K^-1 gamma H_i)[e_r]; kDecDetInv: (1 + gamma^2)^-1 for the kernels that invert both-erased pairs.
-// ns >= 2 (DecKernel::Local256 of (10,4,13) only, local256_batch_geometry holds): that pattern in
-// every one of ns stripes, stripe s = stripe 0's pointers + s * sin (inputs) / s * sout (outputs), in
-// ONE launch of the kernel's BATCH variant ("stream-local256-batch"); the tables go through
-// dec_tables once, nothing else is allocated.
+// ns >= 2 (DecKernel::Local256 or DecKernel::Fused2 of (10,4,13) only, local256_batch_geometry /
+// fused2_batch_geometry holds): that pattern in every one of ns stripes, stripe s = stripe 0's
+// pointers + s * sin (inputs) / s * sout (outputs), in ONE launch of the kernel's BATCH variant
+// ("stream-local256-batch" / "stream-fused2-batch"); the tables go through dec_tables once, nothing
+// else is allocated.
 template <int KD>
 static Error launch_stream_decode(CodeState &cs, const DevProps &prop, const uint8_t *const *cin, uint8_t *const *cout,
                                   const bs::DecChoice &ch, size_t sc, hipStream_t stream, size_t ns = 1, int64_t sin = 0,
@@ -2344,19 +2360,24 @@ static Error launch_stream_decode(CodeState &cs, const DevProps &prop, const uin
         a.region = cut.region;
         a.nslots = cut.nslots;
     } else {
-        a.region = uint32_t(((sc + 7) / 8 + 63) / 64 * 64);
-        a.nslots = std::min(prop.per_xcd(), std::max(1u, a.region / 64u));
+        // 64-byte tiles round robin over an XCD's workgroups
+        const bs::StreamCut cut = bs::round_robin_cut(sc, prop.per_xcd());
+        a.region = cut.region;
+        a.nslots = cut.nslots;
     }
     if (ns >= 2) {
-        if (KD != 10 || ch.kernel != bs::DecKernel::Local256 || !local256_batch_geometry(prop, ns, sc, &a.groups))
+        const bool l256 = ch.kernel == bs::DecKernel::Local256;
+        if (KD != 10 || !(l256 ? local256_batch_geometry(prop, ns, sc, &a.groups)
+                               : f2 && fused2_batch_geometry(prop, ns, sc, &a.groups)))
             return make_error(CLAY_ERR_DEVICE, 0, 0, 0, "streaming decode batch: no kernel for this call");
         a.nstripes = uint32_t(ns);
         a.sin = sin;
         a.sout = sout;
         if (Error e = dec_tables(cs, prop, tabs, stream, &a.tabs)) return e;
-        CLAY_HIP(launch_stream_local256_batch_kernel(KD, ch.G, a, stream, prop.dev));
+        if (l256) CLAY_HIP(launch_stream_local256_batch_kernel(KD, ch.G, a, stream, prop.dev));
+        else CLAY_HIP(launch_stream_fused2_batch_kernel(KD, a, stream, prop.dev, ch.two));
         t_last_launches += 1;
-        t_last_exec = "stream-local256-batch";
+        t_last_exec = l256 ? "stream-local256-batch" : "stream-fused2-batch";
         return Error{};
     }
     if (Error e = dec_tables(cs, prop, tabs, stream, &a.tabs)) return e;
@@ -2581,6 +2602,18 @@ static Error decode_device_impl(const clay_code_t *code, const uint8_t *const *c
 // clay_amd.DECODE_STREAM_BATCH_AUTO_MAX_SC restates it (tests/test_local256_batch_gate_cpu.py).
 constexpr size_t kDecodeStreamBatchMaxSc = 262152;
 
+// The same gate for the batch of the fused decode v2 ("stream-fused2-batch", 3-4 erasures and the
+// 2-erasure patterns "stream" sends to k_stream_fused2): the largest swept sub-chunk up to which the
+// batch's median was at most the loop's plus the spread of the loop's samples in every cell of
+// scripts/bench_paths.py ONLY=batch_decode_fused2_gate (profiles/r15/batch_decode_fused2_gate.txt,
+// DESIGN.md 4.10; 0 would mean auto never takes the batch).  Sub-chunks 1,640 to 419,432, 2 / 4 / 16 /
+// 64 stripes (cells up to 4 GiB of data), erasures {0,4,8,12} and {0,1,4,8}: the batch wins every
+// cell by more than the loop's spread (0.4-7.5 us) -- 64 stripes of 16 MiB 611 vs 2,295 us, two
+// stripes of 1 GiB 972 vs 997 us -- so the gate is the sweep's largest sub-chunk, 419,432; above it
+// nothing was measured and auto keeps one launch per stripe.
+// clay_amd.DECODE_FUSED2_BATCH_AUTO_MAX_SC restates it (tests/test_fused2_batch_gate_cpu.py).
+constexpr size_t kDecodeFused2BatchMaxSc = 419432;
+
 // ---- batched decode: n_stripes stripes with the same erasure set (clay_decode_device_strided /
 // clay_decode_device_batch) ----
 // in / out: the n chunks and the n output buffers of every stripe, both in the same form.  Pointer
@@ -2634,16 +2667,18 @@ static Error decode_batch_impl(const clay_code_t *code, StripeOperands in, const
     CodeState &cs = *o.cs;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int xmode = g_exec_mode.load(std::memory_order_relaxed);
-    // streaming batch: (10,4,13), 2 or more stripes whose pattern runs on k_stream_local256 on
-    // 8-byte rows (one erasure, or two in the shapes local_shape takes, 512 <= sc < 2^24), every
+    // streaming batch: (10,4,13), 2 or more stripes whose pattern runs on k_stream_local256 (one
+    // erasure, or two in the shapes local_shape takes) or on k_stream_fused2 (3-4 erasures, at most
+    // two per section, and the pairs "stream" sends there) on 8-byte rows, 512 <= sc < 2^24, every
     // present input at one stripe stride and every wanted output at one, both multiples of 8:
     // ONE launch of the kernel's BATCH variant for any number of stripes.  "stream": every such
     // call, the stripes of 4 MiB or less included; auto: only where the call would run stripe by
-    // stripe below, by the gate kDecodeStreamBatchMaxSc; no other mode ("stream-local" keeps one
-    // launch per stripe: the A/B partner).
+    // stripe below, by the kernel's gate (kDecodeStreamBatchMaxSc / kDecodeFused2BatchMaxSc); no
+    // other mode ("stream-local" and "stream-fused2" keep one launch per stripe: the A/B partners).
     if (n_stripes >= 2 && tn == 16 && c.k == 10 && c.m == 4 && c.q == 4 && c.t == 4 && chunk % c.sub_chunk_no == 0 &&
-        (xmode == kExecStream || (xmode == kExecAuto && c.k * chunk > kBatchMaxStripeBytes &&
-                                  chunk / c.sub_chunk_no <= kDecodeStreamBatchMaxSc))) {
+        (xmode == kExecStream ||
+         (xmode == kExecAuto && c.k * chunk > kBatchMaxStripeBytes &&
+          chunk / c.sub_chunk_no <= std::max(kDecodeStreamBatchMaxSc, kDecodeFused2BatchMaxSc)))) {
         const uint8_t *cin[16] = {};
         uint8_t *cout[16] = {};
         uint32_t gone_m = 0, alive_m = 0;
@@ -2666,12 +2701,16 @@ static Error decode_batch_impl(const clay_code_t *code, StripeOperands in, const
         int64_t sin = 0, sout = 0;
         uint32_t groups = 0;
         if (!wanted.empty() && uniform_stride(in, 0, n_stripes, present.data(), present.size(), &sin) &&
-            uniform_stride(out, 0, n_stripes, wanted.data(), wanted.size(), &sout) && sin % 8 == 0 && sout % 8 == 0 &&
-            local256_batch_geometry(dev_props(dev), n_stripes, sc, &groups)) {
+            uniform_stride(out, 0, n_stripes, wanted.data(), wanted.size(), &sout) && sin % 8 == 0 && sout % 8 == 0) {
             const bs::DecChoice ch =
                 bs::choose_decode(10, gone_m, alive_m, xmode, sc, !misaligned8(cin, 16) && !misaligned8(cout, 16),
                                   tuning().decode_ring, tuning().local_w64);
-            if (ch.kernel == bs::DecKernel::Local256)
+            const bool gated = xmode == kExecAuto;  // auto: each kernel's own measured gate
+            if (ch.kernel == bs::DecKernel::Local256 && (!gated || sc <= kDecodeStreamBatchMaxSc) &&
+                local256_batch_geometry(dev_props(dev), n_stripes, sc, &groups))
+                return launch_stream_decode<10>(cs, dev_props(dev), cin, cout, ch, sc, st, n_stripes, sin, sout);
+            if (ch.kernel == bs::DecKernel::Fused2 && (!gated || sc <= kDecodeFused2BatchMaxSc) &&
+                fused2_batch_geometry(dev_props(dev), n_stripes, sc, &groups))
                 return launch_stream_decode<10>(cs, dev_props(dev), cin, cout, ch, sc, st, n_stripes, sin, sout);
         }
     }

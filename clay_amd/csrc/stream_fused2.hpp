@@ -27,6 +27,8 @@
 // region take all 160 KiB of LDS.
 #pragma once
 
+#include <type_traits>
+
 #include "stream_decode.hpp"
 
 namespace clay {
@@ -55,9 +57,24 @@ using IC = std::integral_constant<int, N>;
 // TWO: the instantiation for two erasures in a section (both-erased pairs, split steps, the larger
 // round item sets); patterns with at most one erasure per section run TWO = false, whose hot code
 // is the round-5 kernel's (the larger TWO kernel ran {0,4,8,12} 15 % slower: 0.58 vs 0.51 ms)
-template <int KD, int G, int PROBE = 0, bool TWO = false>
+struct F2NoWalk {  // the one-stripe kernels' stand-in for the batch map's walk
+    template <class M>
+    __device__ explicit F2NoWalk(const M &) {}
+};
+// BATCH: many stripes in one launch (decode_fused2_batch.hip): grid = 8 * a.groups * a.nslots;
+// workgroup slot = blockIdx.x / 8 is sub-slot slot % nslots of group slot / nslots, which runs the
+// one-stripe cut of its group's stripes back to back (BatchMapOf<RoundRobinMap>,
+// stream_tile_map.hpp).  Stripe s's nodes are a.node[i] + s * a.sin, its outputs a.out[r] + s *
+// a.sout; the stripe is uniform per tile and goes into the 64-bit uniform base of the loads and the
+// stores.  Nothing else looks at a tile's place: the loaders' flat load counter, the counted waits,
+// the ring, the S/C region's hand-over, the five barriers (and the split steps' second ones), the
+// rounds and pairs() run over the workgroup's concatenated tile sequence unchanged.  Both wave
+// kinds walk the map tile after tile (Walk: no division by the tiles per stripe).
+template <int KD, int G, int PROBE = 0, bool TWO = false, bool BATCH = false>
 __global__ __launch_bounds__((StreamDec<KD, G>::BLOCK)) void k_stream_fused2(DecArgs a) {
     using Kn = StreamDec<KD, G>;
+    static_assert(!BATCH || PROBE == 0, "the batch variant has no probes");
+    using BMap = BatchMapOf<RoundRobinMap>;
     // round work items per lane and level (decode_args.hpp)
     static constexpr int IT[4] = {TWO ? kF2Iters[0] : kF2Iters1[0], TWO ? kF2Iters[1] : kF2Iters1[1],
                                   TWO ? kF2Iters[2] : kF2Iters1[2], TWO ? kF2Iters[3] : kF2Iters1[3]};
@@ -67,9 +84,16 @@ __global__ __launch_bounds__((StreamDec<KD, G>::BLOCK)) void k_stream_fused2(Dec
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint32_t xcd = blockIdx.x & 7u, wslot = blockIdx.x >> 3, ns = a.nslots;
     const uint32_t sc = uint32_t(a.sc);
-    const typename Kn::Map tm(sc, a.region, ns, xcd, wslot);
-    const uint32_t ntile = tm.n;
-    if (ntile == 0) return;  // uniform per workgroup
+    using Map = std::conditional_t<BATCH, BMap, typename Kn::Map>;
+    const Map tm = [&]() BS_INL {
+        if constexpr (BATCH) return Map(sc, a.region, ns, a.groups, a.nstripes, xcd, wslot);
+        else return Map(sc, a.region, ns, xcd, wslot);
+    }();
+    const uint32_t ntile = [&]() BS_INL {
+        if constexpr (BATCH) return uint32_t(tm.ntile());
+        else return tm.n;
+    }();
+    if (ntile == 0) return;  // uniform per workgroup (BATCH: also a slot whose group has no stripe)
     const uint32_t RB = a.ring, NT = a.nt;
     constexpr uint32_t BUF = uint32_t(Kn::BUF);
     uint8_t *const scr = smem + RB * BUF;  // S/C region
@@ -84,11 +108,26 @@ __global__ __launch_bounds__((StreamDec<KD, G>::BLOCK)) void k_stream_fused2(Dec
         const uint32_t lds0 = lds_addr_of(smem);
         const uint32_t nloads = ntile * NT;
         uint32_t issued = 0;
+        // BATCH: the tile of load `issued` (lt) and the load's index in it (lq), stepped with the
+        // counter; the walk is advanced only while a tile is left
+        [[maybe_unused]] std::conditional_t<BATCH, typename BMap::Walk, F2NoWalk> lwalk(tm);
+        [[maybe_unused]] StreamTile lt{};
+        [[maybe_unused]] uint32_t lq = 0;
+        if constexpr (BATCH) lt = lwalk.next(tm);
         auto issue_upto = [&](uint32_t lim) {
             if (lim > nloads) lim = nloads;
             for (; issued < lim; issued++) {
-                const uint32_t k = issued / NT, q = issued % NT;
-                Kn::issue(a, L, lds0 + (issued % RB) * BUF, a.node[a.load_node[q]], tm.tile(k, wslot, ns), li);
+                if constexpr (BATCH) {
+                    Kn::issue(a, L, lds0 + (issued % RB) * BUF, a.node[a.load_node[lq]] + int64_t(lt.stripe) * a.sin,
+                              typename Kn::Tile{lt.b0, lt.vend}, li);
+                    if (++lq == NT) {
+                        lq = 0;
+                        if (issued + 1u < nloads) lt = lwalk.next(tm);
+                    }
+                } else {
+                    const uint32_t k = issued / NT, q = issued % NT;
+                    Kn::issue(a, L, lds0 + (issued % RB) * BUF, a.node[a.load_node[q]], tm.tile(k, wslot, ns), li);
+                }
             }
         };
         issue_upto(RB);
@@ -457,11 +496,21 @@ __global__ __launch_bounds__((StreamDec<KD, G>::BLOCK)) void k_stream_fused2(Dec
     constexpr bool TM = (PROBE & 16) != 0;
     uint64_t tm_pa = 0, tm_pabar = 0, tm_pre = 0, tm_br = 0, tm_rd = 0, tm_bw = 0, tm_st = 0, t0 = 0;
     const uint64_t tm_start = TM ? __builtin_amdgcn_s_memtime() : 0;
+    // BATCH: tile k (phase A) and tile k - 1 (the stores) each from a walk of the map of their own:
+    // two counters each, nothing of a tile kept across the phases
+    [[maybe_unused]] std::conditional_t<BATCH, typename BMap::Walk, F2NoWalk> cwalk(tm), swalk(tm);
     for (uint32_t k = 0; k <= ntile; k++) {
         uint32_t S[32];
         if constexpr (TM) t0 = __builtin_amdgcn_s_memtime();
         if (k < ntile) {
-            const typename Kn::Tile t = tm.tile(k, wslot, ns);
+            const typename Kn::Tile t = [&]() BS_INL {
+                if constexpr (BATCH) {
+                    const StreamTile tc = cwalk.next(tm);
+                    return typename Kn::Tile{tc.b0, tc.vend};
+                } else {
+                    return tm.tile(k, wslot, ns);
+                }
+            }();
             const bool straddle = t.vend < t.b0 + uint32_t(Kn::W) && ((t.vend - t.b0) & 15u) == 8u;
             const uint32_t pcs = (t.vend - t.b0) >> 4;
             const uint32_t poff0 = 8u * p + ((straddle && p == 2u * pcs) ? 8u : 0u);
@@ -563,7 +612,12 @@ __global__ __launch_bounds__((StreamDec<KD, G>::BLOCK)) void k_stream_fused2(Dec
         }
         if (k >= 1 && !(PROBE & 2)) {
             // 8-byte stores: eight lanes (p) write each layer's 64-byte row run of the tile
-            const typename Kn::Tile t = tm.tile(k - 1, wslot, ns);
+            [[maybe_unused]] StreamTile tp{};
+            if constexpr (BATCH) tp = swalk.next(tm);
+            const typename Kn::Tile t = [&]() BS_INL {
+                if constexpr (BATCH) return typename Kn::Tile{tp.b0, tp.vend};
+                else return tm.tile(k - 1, wslot, ns);
+            }();
             const uint32_t pp = opq(p);  // opaque per tile: dst_r + 8 p is not hoisted into 4 x 64-bit registers
             if (t.b0 + 8u * pp + 8u <= t.vend) {
                 const uint32_t z0 = Kn::layer0(opq(c0));
@@ -571,6 +625,7 @@ __global__ __launch_bounds__((StreamDec<KD, G>::BLOCK)) void k_stream_fused2(Dec
                 for (int r = 0; r < 4; r++) {
                     uint8_t *dst = a.out[r];
                     if (uint32_t(r) >= a.ne || !dst) continue;
+                    if constexpr (BATCH) dst += int64_t(tp.stripe) * a.sout;
 #pragma unroll
                     for (int g = 0; g < 4; g++)
                         *reinterpret_cast<uint2 *>(dst + uint64_t(z0 + uint32_t(g) * Kn::wt(G)) * sc + t.b0 + 8u * pp) =

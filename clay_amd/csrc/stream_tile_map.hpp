@@ -1,8 +1,10 @@
 // stream_tile_map.hpp -- how the streaming kernels cut a sub-chunk row of sc bytes into tiles:
-// BalancedMap (k_stream_encode), StreamMap (k_stream_local256 and the other streaming kernels) and
-// the batch grouping over either (BatchMapOf).
+// BalancedMap (k_stream_encode), StreamMap (k_stream_local256 and the other streaming kernels),
+// RoundRobinMap (the 64-byte tiles of k_stream_fused2's batch) and the batch grouping over any of
+// them (BatchMapOf).
 // Plain integer code (no HIP builtins), so that a host program can include it and walk the maps
-// (tests/test_stream_tile_map_cpu.py, tests/test_local256_batch_map_cpu.py).
+// (tests/test_stream_tile_map_cpu.py, tests/test_local256_batch_map_cpu.py,
+// tests/test_fused2_batch_map_cpu.py).
 //
 // BalancedMap.
 // XCD x owns bytes [x * region, min((x + 1) * region, sc)) of every row (region: a multiple of
@@ -99,8 +101,37 @@ struct StreamMap {
     }
 };
 
+// RoundRobinMap (k_stream_fused2 BATCH; the cut of StreamDec::Map, stream_decode.hpp, which the
+// one-stripe decode kernels keep using): XCD x owns bytes [x * region, min((x + 1) * region, sc))
+// (region: a multiple of 64); its 64-byte tiles go round robin over the XCD's ns workgroups, tile
+// k of workgroup `slot` at x0 + (slot + k * ns) * 64, the region's last tile clipped to its end
+// (sc a multiple of 8: a last tile of 8, 16, ... 56 bytes).
+struct RoundRobinMap {
+    static constexpr uint32_t W = 64u;
+    uint32_t x0, x1, n;
+    CLAY_TILE_MAP_HD RoundRobinMap(uint32_t sc, uint32_t region, uint32_t ns, uint32_t xcd, uint32_t slot) {
+        x0 = xcd * region;
+        x1 = x0 + region < sc ? x0 + region : sc;
+        n = 0;
+        if (x0 < x1) {
+            const uint32_t nt = (x1 - x0 + W - 1u) / W;
+            n = nt > slot ? (nt - slot + ns - 1u) / ns : 0u;
+        }
+    }
+    CLAY_TILE_MAP_HD int ntile() const { return int(n); }
+    CLAY_TILE_MAP_HD StreamTile tile(int k, uint32_t slot, uint32_t ns) const {
+        const uint32_t b0 = x0 + (slot + uint32_t(k) * ns) * W;
+        return {b0, b0 + W < x1 ? b0 + W : x1, 0u};
+    }
+};
+
+// ... and the host's cut for it: an XCD's region is sc / 8 rounded up to 64 bytes, with one
+// workgroup per 64-byte tile of a region, at least one and at most per_xcd.
+CLAY_TILE_MAP_HD inline uint32_t round_robin_region(uint64_t sc) { return uint32_t(((sc + 7) / 8 + 63) / 64 * 64); }
+
 // A batch of n_stripes stripes of one sub-chunk size in one launch (k_stream_encode BATCH with
-// One = BalancedMap, k_stream_local256 BATCH with One = StreamMap: BatchMapOf<One>).
+// One = BalancedMap, k_stream_local256 BATCH with One = StreamMap, k_stream_fused2 BATCH with
+// One = RoundRobinMap: BatchMapOf<One>).
 // Every stripe keeps exactly the one-stripe cut: its region, ns = nsS workgroups per XCD and
 // One(sc, region, nsS, xcd, sub); the encode's words below (BalancedMap, rounds) read the same for
 // StreamMap and its tiles.  The per_xcd workgroups of an XCD form
@@ -128,6 +159,12 @@ struct StreamCut {
 CLAY_TILE_MAP_HD inline StreamCut stream_cut(uint64_t sc, uint32_t per_xcd, uint32_t tile = 256u) {
     const uint32_t region = xcd_region(sc);
     const uint32_t tiles = (region + tile - 1u) / tile > 1u ? (region + tile - 1u) / tile : 1u;
+    return {region, per_xcd < tiles ? per_xcd : tiles};
+}
+
+CLAY_TILE_MAP_HD inline StreamCut round_robin_cut(uint64_t sc, uint32_t per_xcd) {
+    const uint32_t region = round_robin_region(sc);
+    const uint32_t tiles = region / 64u > 1u ? region / 64u : 1u;
     return {region, per_xcd < tiles ? per_xcd : tiles};
 }
 
@@ -160,7 +197,7 @@ struct BatchMapOf {
     struct Walk {
         uint32_t r, stripe;
         CLAY_TILE_MAP_HD explicit Walk(const BatchMapOf &m) : r(0u), stripe(m.first) {}
-        CLAY_TILE_MAP_HD StreamTile next(const BatchMapOf &m) {
+        CLAY_TILE_MAP_HD __attribute__((always_inline)) StreamTile next(const BatchMapOf &m) {
             StreamTile t = m.one.tile(int(r), m.sub, m.ns);
             t.stripe = stripe;
             if (++r == m.nt) {

@@ -336,7 +336,23 @@ int clay_decode_device_codeword(const clay_code_t *code, const uint8_t *const *c
  *   "stream-fused2"  unchanged
  * The pattern's table is uploaded once per pattern: inside a stream capture the call needs one warm
  * call of the same pattern first (else the "not prepared" error, nothing launched); nothing else is
- * allocated.  (9,4,12), rows off 8-byte alignment and 3-4 erasures keep the paths above.
+ * allocated.  (9,4,12) and rows off 8-byte alignment keep the paths above.
+ * Three and four erasures -- the batch of the fused decode v2 (k_stream_fused2, last exec path
+ * "stream-fused2-batch", clay_last_launch_count() 1): the same conditions, with a pattern that exec
+ * mode "stream" runs on k_stream_fused2 in the one-stripe call (at most two erasures per y-section
+ * and within the kernel's round capacity: 352 of the 364 three-erasure and 878 of the 1,001
+ * four-erasure patterns of (10,4,13)).  Every stripe keeps the one-stripe cut of 64-byte tiles; the
+ * workgroups left over run further stripes side by side.  Which exec modes take it:
+ *   "stream"         every eligible call at any eligible size, stripes of <= 4 MiB included
+ *   auto             only calls that would run stripe by stripe (more than 4 MiB of data per
+ *                    stripe), for sub-chunks up to the measured gate kDecodeFused2BatchMaxSc
+ *                    = 419,432 bytes, the largest sub-chunk of the sweep: the batch beat the loop in
+ *                    every swept cell (profiles/r15/batch_decode_fused2_gate.txt); above it
+ *                    nothing was measured and auto keeps one launch per stripe
+ *   "stream-fused2"  never: one launch per stripe ("stream-fused2"), the A/B partner
+ *   "stream-local", "grouped", "tile"  never
+ * Warm call before a capture and allocation as above.  (9,4,12), the patterns outside the kernel
+ * and rows off 8-byte alignment keep the paths above.
  * Asynchronous on `stream`. */
 int clay_decode_device_strided(const clay_code_t *code, const uint8_t *chunks, int64_t node_stride,
                                int64_t stripe_stride, const size_t *erasures, size_t n_erasures,
@@ -493,7 +509,8 @@ int clay_set_encode_path(int mode);
  *                the batched k_bs_decode1 ("bs-decode1-batch"), every other code, pattern or
  *                layout, from 4 stripes, one k_gexec launch per plan level for the whole batch
  *                ("grouped-batch"; larger (10,4,13) stripes with one or two erasures: the streaming
- *                batch, "stream-local256-batch", up to the gate of clay_decode_device_strided);
+ *                batch, "stream-local256-batch", up to the gate of clay_decode_device_strided;
+ *                with three or four erasures "stream-fused2-batch" up to its gate there);
  *                batched repairs (clay_repair_device_strided / _batch, same
  *                stripe sizes): q = m codes with a k_bs_repair instantiation from all n - 1 other
  *                nodes at uniform stripe strides in one launch of the batched k_bs_repair
@@ -518,7 +535,8 @@ int clay_set_encode_path(int mode);
  *                the pattern (the (2,1) patterns: the fused decode v2 first), else the fused
  *                decode v2 (2-4 erasures, at most two per section); batched decodes of (10,4,13)
  *                eligible for the streaming batch (clay_decode_device_strided) in one launch,
- *                "stream-local256-batch", at any eligible size; everything else as auto
+ *                "stream-local256-batch" or, on the fused decode v2, "stream-fused2-batch", at any
+ *                eligible size; everything else as auto
  *   5 stream-local -- every decode a local kernel takes on it ("stream-local256" /
  *                "stream-local", the (2,1) patterns included); every other decode on auto's
  *                plan executors (no fused decode v2, no k_bs_decode1); never the streaming batch
@@ -528,7 +546,8 @@ int clay_set_encode_path(int mode);
  *                section's surviving real nodes fit it, two neighbouring sections that do not
  *                run as a split step; the loader waves' round items fit their registers);
  *                every other decode, one erasure included, on auto's plan executors (no local
- *                decode, no k_bs_decode1)
+ *                decode, no k_bs_decode1); batched decodes keep one launch per stripe (the A/B
+ *                partner of "stream-fused2-batch")
  * (4 and 7 are retired: the single-launch decode of round 3 and the process-wide "codeword"
  * mode, now the per-call clay_decode_device_codeword.)
  * No CLAY_* environment variable is read on a call path; the measurement knobs (planner and

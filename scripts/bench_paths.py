@@ -10,6 +10,8 @@ ONLY=batch_stream: many (10,4,13) stripes above 4 MiB per call, the streaming ba
 per-stripe loop; batch_stream_gate: the sweep behind auto's upper gate for it.
 ONLY=scrub_batch_stream: many (10,4,13) stripes scrubbed in one launch of the streaming batch, the
 path without it and the batched encode alternated; scrub_batch_gate: the sweep behind auto's gate.
+ONLY=batch_decode_fused2 / batch_decode_fused2_gate: the same with three and four lost nodes, one
+launch of the fused decode v2's batch against the per-stripe loop, and the sweep behind auto's gate.
 ONLY=batch_decode_stream: many (10,4,13) stripes with the same lost nodes decoded in one launch of
 the local decode's batch variant against the per-stripe loop; batch_decode_stream_gate: the sweep
 behind auto's gate for it.
@@ -479,8 +481,11 @@ def batch_stream_cfg(sc, n, k=10, m=4, d=13, gate=False):
     print(json.dumps(out), flush=True)
 
 
-def batch_decode_stream_cfg(sc, n, er, gate=False, samples=None):
-    """ONLY=batch_decode_stream / batch_decode_stream_gate: n stripes of (10,4,13) at sub-chunk sc
+def batch_decode_stream_cfg(sc, n, er, gate=False, samples=None, loop_mode="stream-local", name="batch_decode_stream"):
+    """ONLY=batch_decode_fused2 / batch_decode_fused2_gate (loop_mode "stream-fused2"): the same A/B
+    for three and four lost nodes -- ONE launch of the fused decode v2's batch variant (exec mode
+    "stream", "stream-fused2-batch") against n launches of "stream-fused2".
+    ONLY=batch_decode_stream / batch_decode_stream_gate: n stripes of (10,4,13) at sub-chunk sc
     with the nodes `er` lost in every stripe through clay_decode_device_strided, as ONE launch of the
     local decode's batch variant (exec mode "stream", "stream-local256-batch") and as the library's
     per-stripe loop (exec mode "stream-local", n launches of "stream-local256": the path without the
@@ -502,7 +507,7 @@ def batch_decode_stream_cfg(sc, n, er, gate=False, samples=None):
             c.decode_device_strided(full, er, outs, n, chunk, 0, 0, 0, 0, 0, stream.cuda_stream)
         return fn
 
-    legs = [("batch", call("stream")), ("loop", call("stream-local"))]
+    legs = [("batch", call("stream")), ("loop", call(loop_mode))]
     keep = RUNS
     if samples:
         RUNS = samples
@@ -529,7 +534,7 @@ def batch_decode_stream_cfg(sc, n, er, gate=False, samples=None):
                 torch.cuda.synchronize()
                 if i >= 2:
                     ts[tag].append(e0.elapsed_time(e1) / B2B)
-        out = {"config": f"decode (10,4,13) batch_decode_stream {n} x {k * chunk / 2**20:.1f} MiB (sc {sc}) erasures {er}",
+        out = {"config": f"decode (10,4,13) {name} {n} x {k * chunk / 2**20:.1f} MiB (sc {sc}) erasures {er}",
                "stripe_data_bytes": n * k * chunk}
         for tag, _ in legs:
             t = ts[tag]
@@ -696,6 +701,19 @@ if __name__ == "__main__":
                 sc, n, er, gate=True, samples=max(5, RUNS // 2))))
               for sc in (1640, 2048, 6560, 26216, 66176, 131080, 262152, 419432) for n in (2, 4, 16, 64)
               if n * 2560 * sc <= 4 << 30 for er in ([0], [0, 4])],
+            # ONLY=batch_decode_fused2: 1 GiB of (10,4,13) data as 64 stripes of 16 MiB, 205 of 5 MiB and
+            # 16 of 64 MiB with four, three and (the TWO instantiation) two-in-a-section lost nodes:
+            # the batch under "stream" against the per-stripe loop under "stream-fused2" 
+            *[("batch_decode_fused2", (lambda sc=sc, n=n, er=er: batch_decode_stream_cfg(
+                sc, n, er, loop_mode="stream-fused2", name="batch_decode_fused2")))
+              for er in ([0, 4, 8, 12], [0, 4, 8], [0, 1, 4, 8]) for sc, n in ((6560, 64), (2048, 205), (26216, 16))],
+            # ONLY=batch_decode_fused2_gate: the sweep behind auto's gate for that batch: the
+            # sub-chunks, stripe counts and rule of batch_decode_stream_gate, patterns {0,4,8,12}
+            # and {0,1,4,8}
+            *[("batch_decode_fused2_gate", (lambda sc=sc, n=n, er=er: batch_decode_stream_cfg(
+                sc, n, er, gate=True, samples=max(5, RUNS // 2), loop_mode="stream-fused2", name="batch_decode_fused2")))
+              for sc in (1640, 2048, 6560, 26216, 66176, 131080, 262152, 419432) for n in (2, 4, 16, 64)
+              if n * 2560 * sc <= 4 << 30 for er in ([0, 4, 8, 12], [0, 1, 4, 8])],
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 1 << 10, 65536, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 10 << 10, 6553, 0, 1024)),
             ("batch_decode", lambda: decode_batch_cfg(4, 2, 5, 100 << 10, 655, 0, 655)),
